@@ -4,6 +4,8 @@
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full      # + kernel timings and rooflines, the reference's own shapes, CPU baseline
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR      # + the last timed step's outputs as DIR/*.npy
 
 A step = one full reference step (/root/reference/src/traintest_cavmae_base.py:131-152) on one per-GPU batch:
 contrastive pass fwd+bwd -> grad all-reduce -> Adam#1 -> MAE pass fwd+bwd -> grad all-reduce -> Adam#2, including
@@ -371,6 +373,27 @@ def secondary_shapes(args, dev):
     return out
 
 
+def dump_outputs(model, last, out_dir, per_tensor=16384):
+    """What the timed step hands its caller, for output-for-output comparison of two builds on identical inputs:
+      losses.npy      float64 [5]  the last timed step's (loss_pass2, loss_mae_a, loss_mae_v, loss_c, c_acc)
+      parameters.npy  float32      the parameters after that step's Adam updates: every tensor in name order, up to `per_tensor`
+                                   elements each at positions drawn from a generator seeded by the tensor's name (independent of how
+                                   the parameters are laid out in memory; 12 MB at ViT-B)"""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "losses.npy"), np.array([float(x.item()) for x in last], dtype=np.float64))
+    parts = []
+    with torch.no_grad():
+        for name, p in sorted(model.named_parameters()):
+            flat = p.detach().reshape(-1)
+            if flat.numel() > per_tensor:
+                idx = torch.randint(flat.numel(), (per_tensor,), generator=torch.Generator().manual_seed(zlib.crc32(name.encode())))
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "parameters.npy"), torch.cat(parts).numpy())
+
+
 def log(msg):
     if int(os.environ.get("RANK", 0)) == 0:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -403,6 +426,12 @@ def main():
     ap.add_argument("--force-dp", action="store_true", help="form the RCCL process group and issue EVERY collective of the data-parallel step "
                     "(packed embedding all-gather, chunked overlapped gradient all-reduce) even at world size 1 - the most of the multi-GPU "
                     "path a one-GPU box can execute; AVSIAM_COMM=rccl selects the C ABI's communicator, AVSIAM_DP_WIRE=bf16 the bf16 wire")
+    ap.add_argument("--full", action="store_true", help="measure more than the headline line: HIP-event kernel timings in the timed region "
+                    "(`roofline`, `kernels`), the single-stream pass after it (`roofline_more`), the reference's own shapes (`secondary`) and "
+                    "the CPU baseline (`cpu_baseline`); the options below shape these parts.  Without it a run only sets up, warms up, times "
+                    "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed into DIR as .npy "
+                    "files (dump_outputs: the losses and a fixed, seeded sample of the updated parameters)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--roofline-steps", type=int, default=2, help="steps of the separate single-stream pass that times the other kernel families")
     ap.add_argument("--no-kernel-events", action="store_true")
@@ -416,6 +445,8 @@ def main():
     ap.add_argument("--dry-run-launch", action="store_true", help="with --gpus N > 1 outside torch.distributed.run: print the launch command and "
                     "the environment the ranks would get as one JSON line, start nothing (tests/test_bench_launcher_cpu.py)")
     args = ap.parse_args()
+    if args.all_kernel_events and not args.full:
+        ap.error("--all-kernel-events times kernels, which only a --full run does")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:], dry_run=args.dry_run_launch))
     # stdout carries exactly ONE line, the JSON: whatever libraries print on the way (RCCL's version banner when a process group
@@ -542,7 +573,7 @@ def main():
         torch.cuda.synchronize()
         log(f"warm-up step {i} done, mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
     sync()
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         # default: every 5th gemm_nt launch (282 per step, co-prime to 5: over 5 or 10 steps every launch position is timed
         # equally often); --all-kernel-events: every launch of every kernel family (costs ~5 ms/step of event overhead)
         ops.prof = ops.KernelProfiler() if args.all_kernel_events else ops.KernelProfiler(("gemm_nt",), stride=5)
@@ -554,12 +585,14 @@ def main():
     dt = time.perf_counter() - t0
     log(f"timed region: {args.steps} steps in {dt:.3f} s")
     prof, ops.prof = ops.prof, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, last, args.dump_outputs)
     # The other kernels that matter: weight-gradient GEMM, decoder attention (hd 32), LayerNorm backward.  In the timed
     # region the weight gradients run on a second stream beside attention / LayerNorm backward, so a launch-to-end time there
     # includes waiting for CUs.  Their rooflines are therefore taken in a short SEPARATE pass after the timed region, with
     # everything on one stream (EngineOptions.wgrad_stream "0") and HIP events around every launch of those families.
     prof2 = None
-    if not args.no_kernel_events and world == 1 and args.roofline_steps > 0:
+    if args.full and not args.no_kernel_events and world == 1 and args.roofline_steps > 0:
         mode = model.options.wgrad_stream
         model.set_options(wgrad_stream="0")
         train_step(model, a, v, args.lr)
@@ -595,7 +628,7 @@ def main():
              "pool": ({"share_pass_buffers": True, "activation_pool_gib": round(model._pool.nbytes() / 2 ** 30, 2),
                        "activation_pool_live_gib_last_pass": round(model._pool.used() / 2 ** 30, 2)} if args.share_pass_buffers and model._pool is not None else {})}
     secondary = None
-    if world == 1 and not args.force_dp and args.secondary_steps > 0 and args.model == "vit_base" and not (args.fp8 or args.recompute):
+    if args.full and world == 1 and not args.force_dp and args.secondary_steps > 0 and args.model == "vit_base" and not (args.fp8 or args.recompute):
         import gc
         model.release_buffers()
         model = last = None
@@ -716,7 +749,7 @@ def main():
                                      "kernels": [m for m in more if m], "ms_per_step_by_family": fams,
                                      "kernel_sum_ms_per_step": round(sum(fams.values()), 3),
                                      "launches_per_step": sum(x["launches"] for x in s2.values()) // args.roofline_steps}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the CPU baseline (oracle) on the host cores")
             try:
                 line["cpu_baseline"] = cpu_baseline(cfg)

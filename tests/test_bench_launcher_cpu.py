@@ -112,3 +112,25 @@ def test_counter_summaries_are_attached_only_for_the_source_and_workload_they_we
         (fake_root / "profiles" / "r05" / name).write_text(open(os.path.join(ROOT, "profiles", "r05", name)).read())
     monkeypatch.setattr(bench, "ROOT", str(fake_root))
     assert bench.pmc_traffic(head) is None and not bench.pmc_source(head)
+
+
+def test_dumped_outputs_are_a_fixed_sample_of_what_the_step_returns(tmp_path):
+    """bench.dump_outputs: the losses in float64 and, per parameter in name order, the same seeded positions on every call - so that the
+    dumps of two builds on the same inputs can be compared element for element - within the 64 MB the comparison allows."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from avsiam_amd.config import AVSiamConfig
+    from avsiam_amd.models import CAVMAE_BASE
+    m = CAVMAE_BASE(cfg=AVSiamConfig(audio_tokens=128, frames=1), init_seed=3, init_mode="random", verbose=False)
+    last = tuple(torch.tensor(x) for x in (1.5, 0.75, 0.25, 2.0, 0.5))
+    bench.dump_outputs(m, last, str(tmp_path / "a"))
+    bench.dump_outputs(m, last, str(tmp_path / "b"))
+    la, pa = np.load(tmp_path / "a" / "losses.npy"), np.load(tmp_path / "a" / "parameters.npy")
+    assert la.dtype == np.float64 and la.tolist() == [1.5, 0.75, 0.25, 2.0, 0.5]
+    params = sorted(m.named_parameters())
+    assert pa.dtype == np.float32 and pa.size == sum(min(p.numel(), 16384) for _, p in params) and pa.nbytes < 64 * 2 ** 20
+    assert np.array_equal(pa, np.load(tmp_path / "b" / "parameters.npy"))
+    name, p = params[0]
+    assert p.numel() <= 16384 and np.array_equal(pa[:p.numel()], p.detach().reshape(-1).numpy())

@@ -377,6 +377,25 @@ def test_bench_force_dp_issues_every_collective_on_a_one_rank_rccl_group(env):
     assert all(v == v and abs(v) < 1e4 for v in d["final_losses"].values()), d["final_losses"]
 
 
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the line carries the headline figures and none of the --full
+    measurements, and DIR holds the last timed step's losses (the line's `final_losses`) and a sample of the updated parameters."""
+    import json
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--frames", "1",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-1500:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "samples/s" and d["dtype"] == "bf16"
+    assert not {"roofline", "roofline_more", "kernels", "secondary", "cpu_baseline"} & set(d), sorted(d)
+    losses = np.load(tmp_path / "losses.npy")
+    params = np.load(tmp_path / "parameters.npy")
+    assert losses.dtype == np.float64 and params.dtype == np.float32 and np.isfinite(params).all()
+    assert np.array_equal(losses, np.array(list(d["final_losses"].values())))
+
+
 def test_bench_gpus_2_launches_its_own_ranks():
     """`python bench.py --gpus 2` the way the driver's scaling run would start it - no launcher around it: the parent (no GPU call)
     starts two ranks as a child torch.distributed.run, the ranks run the WORLD_SIZE = 2 branches of the script and of the engine (rank

@@ -9,13 +9,13 @@ set -e
 TAG=${1:-final}
 OUT=$PWD/gpurun_out
 mkdir -p $OUT
-python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-python bench.py --frames 1 --no-cpu-baseline > $OUT/${TAG}_bench_T1.json 2>> $OUT/${TAG}_bench.err
+python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --full --frames 1 --no-cpu-baseline > $OUT/${TAG}_bench_T1.json 2>> $OUT/${TAG}_bench.err
 REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o k -- python3 $REPO/bench.py --steps 4 --warmup 2 --no-cpu-baseline --roofline-steps 0 > $OUT/${TAG}_bench_rocprof.json 2> $OUT/${TAG}_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o k -- python3 $REPO/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --roofline-steps 0 > $OUT/${TAG}_bench_rocprof.json 2> $OUT/${TAG}_rocprof.err
 export AVSIAM_WGRAD_STREAM=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_s0 -o k -- python3 $REPO/bench.py --steps 4 --warmup 2 --no-cpu-baseline --roofline-steps 0 > $OUT/${TAG}_s0_bench_rocprof.json 2> $OUT/${TAG}_s0_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_s0 -o k -- python3 $REPO/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --roofline-steps 0 > $OUT/${TAG}_s0_bench_rocprof.json 2> $OUT/${TAG}_s0_rocprof.err
 unset AVSIAM_WGRAD_STREAM
 cd $REPO
 find $OUT/${TAG}_prof -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_kernel_stats.csv \;
