@@ -88,6 +88,28 @@ class ParamArena:
             self.g = self.pb = self.wt = None
         return self
 
+    def enable_training(self):
+        """Give an arena built with transposed=False, grads=False (an inference-only model) what a backward needs: the transposed bf16
+        copies of the Linear weights and the flat gradient buffer, allocated on the arena's device and filled (shadows) now.  Idempotent;
+        True when something was allocated."""
+        if self.with_grads and (self.t_total or not any(_needs_transpose(self.info[n]) for n in self.names)):
+            return False
+        if not self.t_offset:
+            toff = 0
+            for name in self.names:
+                if _needs_transpose(self.info[name]):
+                    self.t_offset[name] = toff
+                    toff += (math.prod(self.info[name].shape) + ALIGN - 1) // ALIGN * ALIGN
+            self.t_total = toff
+        self.with_grads = True
+        self._tr_tables = {}              # (an inference refresh cached an empty transpose table)
+        if self.p.is_cuda:
+            if self.g is None:
+                self.g = torch.zeros(self.live_end, dtype=torch.float32, device=self.p.device)
+            self.wt = torch.zeros(self.t_total, dtype=torch.bfloat16, device=self.p.device)
+            self.refresh_shadows(None)
+        return True
+
     def ensure_grads(self):
         """Allocate the flat gradient buffer on the arena's device (CPU arenas get one lazily: only the host-side
         DP plumbing tests need it there)."""

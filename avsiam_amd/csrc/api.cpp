@@ -19,6 +19,10 @@ extern "C" const char* avs_last_error(void) { return g_err; }
 
 // 2 (round 6): avs_attn_fwd / avs_attn_bwd need 16-byte-aligned rows (ldo % 8 == 0; was % 4), avs_gemm_nt_fp8 gives out_f32 == 2 / a_e5m2 == 2
 // a meaning (gelu'(x) as 8-bit codes), "ln_dma" is 0 | 1, the deterministic-reduction knob "det" exists
+// still 2 after the fine-tuning entries, which only ADD to the ABI (no existing signature or meaning changed, so a host built against 2 keeps
+// working): avs_cls_loss, avs_segment_mean_bwd_acc (the accumulate form of avs_segment_mean_bwd) and the classifier-head widths
+// D = 1536 / 2048 / 2560 of avs_layernorm_bwd (rejected with -2 before).  A host that needs them checks for the symbols; the new widths of
+// the existing avs_layernorm_bwd came with avs_cls_loss, so a library that exports avs_cls_loss accepts them (one symbol check covers all three).
 extern "C" int avs_abi_version(void) { return 2; }
 
 // number of compute units of the current device (used by hosts to size split factors); <0 on error

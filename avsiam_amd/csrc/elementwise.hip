@@ -244,7 +244,9 @@ __global__ __launch_bounds__(256) void segment_mean_fwd_kernel(const float* __re
     }
 }
 
-// dy[r] = scale * dreps[row_map ? row_map[seg(r)] : seg(r)] / len(seg)
+// dy[r] = scale * dreps[row_map ? row_map[seg(r)] : seg(r)] / len(seg)       (ACC: dy[r] += ..., the fine-tuned model's pooled heads adding to
+// the gradient the fusion blocks left on the same token rows - cav_mae_base.py:1011-1012 beside :1014-1023)
+template <bool ACC = false>
 __global__ void segment_mean_bwd_kernel(const float* __restrict__ dreps, const int* __restrict__ seg_start, float* __restrict__ dy,
                                         int D, float scale, const int* __restrict__ row_map) {
     const int s = blockIdx.x;
@@ -253,7 +255,15 @@ __global__ void segment_mean_bwd_kernel(const float* __restrict__ dreps, const i
     for (int c = threadIdx.x; c < D / 4; c += blockDim.x) {
         float4 v = reinterpret_cast<const float4*>(dreps + (size_t)(row_map ? row_map[s] : s) * D)[c];
         v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
-        for (int r = r0; r < r1; ++r) reinterpret_cast<float4*>(dy + (size_t)r * D)[c] = v;
+        for (int r = r0; r < r1; ++r) {
+            float4* d = reinterpret_cast<float4*>(dy + (size_t)r * D) + c;
+            if (ACC) {
+                const float4 o = *d;
+                *d = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+            } else {
+                *d = v;
+            }
+        }
     }
 }
 
@@ -825,8 +835,18 @@ extern "C" int avs_segment_mean_fwd(const float* y, const int* seg_start, float*
 extern "C" int avs_segment_mean_bwd(const float* dreps, const int* seg_start, float* dy, int nseg, int D, float scale, const int* row_map,
                                     hipStream_t stream) {
     AVS_CHECK_ARG(nseg > 0 && (D % 4) == 0, "segment_mean_bwd: bad args");
-    segment_mean_bwd_kernel<<<nseg, 256, 0, stream>>>(dreps, seg_start, dy, D, scale, row_map);
+    segment_mean_bwd_kernel<false><<<nseg, 256, 0, stream>>>(dreps, seg_start, dy, D, scale, row_map);
     AVS_LAUNCH_CHECK("segment_mean_bwd");
+    return 0;
+}
+
+// accumulate != 0: dy[r] += ... instead of dy[r] = ... (a segment's rows are written by one workgroup: no atomics)
+extern "C" int avs_segment_mean_bwd_acc(const float* dreps, const int* seg_start, float* dy, int nseg, int D, float scale, const int* row_map,
+                                        int accumulate, hipStream_t stream) {
+    AVS_CHECK_ARG(nseg > 0 && (D % 4) == 0 && dreps && seg_start && dy, "segment_mean_bwd_acc: bad args");
+    if (accumulate) segment_mean_bwd_kernel<true><<<nseg, 256, 0, stream>>>(dreps, seg_start, dy, D, scale, row_map);
+    else segment_mean_bwd_kernel<false><<<nseg, 256, 0, stream>>>(dreps, seg_start, dy, D, scale, row_map);
+    AVS_LAUNCH_CHECK("segment_mean_bwd_acc");
     return 0;
 }
 

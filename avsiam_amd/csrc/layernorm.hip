@@ -431,6 +431,64 @@ __global__ void ln_bwd_reduce_kernel(const float* __restrict__ ws, int nblocks, 
     atomicAdd(dst + c, s);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// LayerNorm backward at the classifier-head widths (mlp_head_mm normalises the concatenated audio | video feature: 2 D = 1536 / 2048 / 2560,
+// cav_mae_base.py:812-813,1031).  Few rows (one per clip), so plain kernels: one block per row for dx, then one thread per column summing
+// the rows in order for dg / db (one writer per element, accumulated: +=).  Same arithmetic as ln_bwd_kernel.
+__global__ __launch_bounds__(256) void ln_bwd_head_dx_kernel(const void* __restrict__ dy, int dy_f32, const float* __restrict__ x,
+                                                            const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                            const float* __restrict__ g0, const float* __restrict__ g1,
+                                                            const uint8_t* __restrict__ row_mod, const int* __restrict__ out_map,
+                                                            const void* __restrict__ dres, int dres_bf16, float* __restrict__ dx,
+                                                            bf16_t* __restrict__ dx_bf16, int D) {
+    __shared__ float red[4][2];
+    const int row = blockIdx.x, w = threadIdx.x >> 6;
+    const int drow = out_map ? out_map[row] : row;
+    const float* g = (row_mod && row_mod[row]) ? g1 : g0;
+    const float mean = mean_in[row], rs = rstd_in[row];
+    auto dyv = [&](int c) { return dy_f32 ? reinterpret_cast<const float*>(dy)[(size_t)drow * D + c]
+                                          : bf2f(reinterpret_cast<const bf16_t*>(dy)[(size_t)drow * D + c]); };
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = threadIdx.x; c < D; c += 256) {
+        const float xh = (x[(size_t)row * D + c] - mean) * rs, gy = dyv(c) * g[c];
+        s1 += gy;
+        s2 += gy * xh;
+    }
+    s1 = wave_sum(s1); s2 = wave_sum(s2);
+    if ((threadIdx.x & 63) == 0) { red[w][0] = s1; red[w][1] = s2; }
+    __syncthreads();
+    const float m1 = ((red[0][0] + red[1][0]) + (red[2][0] + red[3][0])) / D;
+    const float m2 = ((red[0][1] + red[1][1]) + (red[2][1] + red[3][1])) / D;
+    for (int c = threadIdx.x; c < D; c += 256) {
+        const float xh = (x[(size_t)row * D + c] - mean) * rs, gy = dyv(c) * g[c];
+        float o = rs * (gy - m1 - xh * m2);
+        if (dres) o += dres_bf16 ? bf2f(reinterpret_cast<const bf16_t*>(dres)[(size_t)row * D + c]) : reinterpret_cast<const float*>(dres)[(size_t)row * D + c];
+        if (dx) dx[(size_t)row * D + c] = o;
+        if (dx_bf16) dx_bf16[(size_t)row * D + c] = f2bf(o);
+    }
+}
+
+__global__ __launch_bounds__(256) void ln_bwd_head_param_kernel(const void* __restrict__ dy, int dy_f32, const float* __restrict__ x,
+                                                               const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                               const uint8_t* __restrict__ row_mod, const int* __restrict__ out_map,
+                                                               float* dg0, float* db0, float* dg1, float* db1, int rows, int D) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= D) return;
+    float g0s = 0.f, b0s = 0.f, g1s = 0.f, b1s = 0.f;
+    for (int r = 0; r < rows; ++r) {
+        const int drow = out_map ? out_map[r] : r;
+        const float d = dy_f32 ? reinterpret_cast<const float*>(dy)[(size_t)drow * D + c] : bf2f(reinterpret_cast<const bf16_t*>(dy)[(size_t)drow * D + c]);
+        const float dxh = d * (x[(size_t)r * D + c] - mean_in[r]) * rstd_in[r];
+        if (row_mod && row_mod[r]) { g1s += dxh; b1s += d; } else { g0s += dxh; b0s += d; }
+    }
+    if (dg0) dg0[c] += g0s;
+    if (db0) db0[c] += b0s;
+    if (dg1) dg1[c] += g1s;
+    if (db1) db1[c] += b1s;
+}
+
+static bool ln_head_width(int D) { return D == 1536 || D == 2048 || D == 2560; }
+
 extern "C" int avs_layernorm_ws_floats(int rows, int D) { return ceil_div(rows, 4 * LN_MIN_ROWS_PER_WAVE) * LN_SETS * D; }
 
 // rows per wave of the backward kernels: a block of 4 waves x RPW rows writes one slab of parameter-gradient partial sums; fewer rows per wave = more
@@ -519,8 +577,18 @@ extern "C" int avs_layernorm_bwd(const void* dy, int dy_f32, const float* x, con
                                  const void* dres, int dres_bf16, float* dx, bf16_t* dx_bf16, float* dg0, float* db0, float* dg1,
                                  float* db1, float* dcol, float* ws, int rows, int D, uint8_t* dx8, float* q8, hipStream_t stream) {
     AVS_CHECK_ARG((dx8 == nullptr) == (q8 == nullptr), "layernorm_bwd: dx8 and its record go together");
-    AVS_CHECK_ARG(rows > 0 && (D == 512 || D == 768 || D == 1024 || D == 1280), "layernorm_bwd: unsupported rows=%d D=%d", rows, D);
+    AVS_CHECK_ARG(rows > 0 && (D == 512 || D == 768 || D == 1024 || D == 1280 || ln_head_width(D)), "layernorm_bwd: unsupported rows=%d D=%d", rows, D);
     AVS_CHECK_ARG(dy && x && mean && rstd && g0 && (dx || dx_bf16) && ws, "layernorm_bwd: null pointer");
+    if (ln_head_width(D)) {              // the classifier-head widths: their own kernels (no slab workspace, no deferred reduce, no e4m3 copy, no dcol)
+        AVS_CHECK_ARG(!dx8 && !dcol && (dg0 || db0 || dg1 || db1), "layernorm_bwd: at D=%d (classifier head) no dx8 / dcol, and the parameter "
+                      "gradients are reduced in the call", D);
+        AVS_CHECK_ARG(!row_mod || g1, "layernorm_bwd: row_mod given without second affine set");
+        ln_bwd_head_dx_kernel<<<rows, 256, 0, stream>>>(dy, dy_f32, x, mean, rstd, g0, g1, row_mod, out_map, dres, dres_bf16, dx, dx_bf16, D);
+        AVS_LAUNCH_CHECK("layernorm_bwd_head");
+        ln_bwd_head_param_kernel<<<ceil_div(D, 256), 256, 0, stream>>>(dy, dy_f32, x, mean, rstd, row_mod, out_map, dg0, db0, dg1, db1, rows, D);
+        AVS_LAUNCH_CHECK("layernorm_bwd_head_param");
+        return 0;
+    }
     AVS_CHECK_ARG(!(dres && dres_bf16 && (const void*)dx_bf16 == dres), "layernorm_bwd: dx_bf16 must not alias a bf16 dres");
     const int rpw = ln_bwd_rpw(rows);
     const int nblocks = ceil_div(rows, 4 * rpw);

@@ -229,6 +229,65 @@ __global__ void infonce_dlogits_kernel(const float* __restrict__ total, const fl
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Classification loss of the fine-tuning loop (src/traintest_ft_base.py:105-110,156-160 of the reference), one block per row of logits:
+//   kind 0  BCEWithLogitsLoss, mean over n * L:  l = max(x,0) - x y + log1p(exp(-|x|)),   dl/dx = (sigmoid(x) - y) / (n L)
+//   kind 1  CrossEntropyLoss with probability targets, mean over n:  l = sum_j y_j (lse(x) - x_j),   dl/dx = (softmax(x) sum_j y_j - y) / n
+// row_loss[r] = the row's sum (fixed per-thread stride, fixed wave / block order: the same bits every run); dx = gout[0] * weight * dl/dx.
+__global__ __launch_bounds__(256) void cls_loss_rows_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ y, long long ldy,
+                                                            int L, int kind, const float* __restrict__ gout, float weight, float inv_norm,
+                                                            float* __restrict__ row_loss, float* __restrict__ dx, long long ldd) {
+    __shared__ float red[4][2];
+    const int r = blockIdx.x, w = threadIdx.x >> 6;
+    const float* xr = x + (size_t)r * ldx;
+    const float* yr = y + (size_t)r * ldy;
+    const float coef = (gout ? gout[0] : 1.0f) * weight * inv_norm;
+    if (kind == 0) {
+        float s = 0.f;
+        for (int j = threadIdx.x; j < L; j += blockDim.x) {
+            const float v = xr[j], t = yr[j];
+            const float e = expf(-fabsf(v));
+            s += fmaxf(v, 0.f) - v * t + log1pf(e);
+            const float sig = v >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+            if (dx) dx[(size_t)r * ldd + j] = coef * (sig - t);
+        }
+        s = wave_sum(s);
+        if ((threadIdx.x & 63) == 0) red[w][0] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) row_loss[r] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        return;
+    }
+    float m = -INFINITY;
+    for (int j = threadIdx.x; j < L; j += blockDim.x) m = fmaxf(m, xr[j]);
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) red[w][0] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
+    __syncthreads();
+    float se = 0.f, sy = 0.f;
+    for (int j = threadIdx.x; j < L; j += blockDim.x) {
+        se += expf(xr[j] - m);
+        sy += yr[j];
+    }
+    se = wave_sum(se); sy = wave_sum(sy);
+    if ((threadIdx.x & 63) == 0) { red[w][0] = se; red[w][1] = sy; }
+    __syncthreads();
+    se = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    sy = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    __syncthreads();
+    const float lse = logf(se);                                  // log-sum-exp of x - m
+    float s = 0.f;                                               // sum_j y_j (lse - (x_j - m)): every term >= 0 for y >= 0, no cancellation
+    for (int j = threadIdx.x; j < L; j += blockDim.x) {
+        const float z = xr[j] - m, t = yr[j];
+        s += t * (lse - z);
+        if (dx) dx[(size_t)r * ldd + j] = coef * (expf(z - lse) * sy - t);
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[w][0] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) row_loss[r] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+}
+
 // ===================================================================================================
 int avs_make_xf(const avs_input_xf_t* x, int want_kind, InXf* out, const char* who);     // elementwise.hip
 
@@ -333,5 +392,19 @@ extern "C" int avs_infonce_dlogits(const float* total, const float* stats, const
     AVS_CHECK_ARG(N > 0 && total && stats && gout && dtotal, "infonce_dlogits: bad args");
     infonce_dlogits_kernel<<<N, 256, 0, stream>>>(total, stats, N, gout, weight, dtotal);
     AVS_LAUNCH_CHECK("infonce_dlogits");
+    return 0;
+}
+
+// logits [n, L] (row stride ldx) and targets [n, L] (ldy) -> loss[0] = weight * mean loss (device scalar: per-row sums, then ONE ordered
+// single-block sum - no float atomics) and, when dx is not NULL, dx [n, L] (ldd) = gout[0] * weight * d(mean loss)/d(logits) (gout NULL: 1)
+extern "C" int avs_cls_loss(const float* x, long long ldx, const float* y, long long ldy, int n, int L, int kind, const float* gout, float weight,
+                            float* row_loss, float* loss, float* dx, long long ldd, hipStream_t stream) {
+    AVS_CHECK_ARG(n > 0 && L > 0 && x && y && row_loss && loss && ldx >= L && ldy >= L && (!dx || ldd >= L) && (kind == 0 || kind == 1),
+                  "cls_loss: bad args (n=%d L=%d kind=%d)", n, L, kind);
+    const float inv_norm = kind == 0 ? 1.0f / ((float)n * (float)L) : 1.0f / (float)n;
+    cls_loss_rows_kernel<<<n, 256, 0, stream>>>(x, ldx, y, ldy, L, kind, gout, weight, inv_norm, row_loss, dx, ldd);
+    AVS_LAUNCH_CHECK("cls_loss_rows");
+    sum_scale_kernel<<<1, 256, 0, stream>>>(row_loss, n, inv_norm * weight, loss, nullptr, 0);
+    AVS_LAUNCH_CHECK("cls_loss_sum");
     return 0;
 }

@@ -53,14 +53,16 @@ class Encoder:
     """The shared ViT over a packed batch of full sequences: `na` audio sequences (La tokens, '_a' norms) followed by
     `nv` frame sequences (Lv tokens, '_v' norms), then the per-modality final norm (cav_mae_base.py:832-841,853-860)."""
 
-    def __init__(self, arena, cfg: AVSiamConfig, na, nv, blocks, final, dev):
+    def __init__(self, arena, cfg: AVSiamConfig, na, nv, blocks, final, dev, inference=True, pool=None, opts=None):
+        """inference=False (ft_train.py): the stack keeps its activations for a backward (pool / opts: engine.Stack)."""
         D, La, Lv = cfg.embed_dim, cfg.audio_tokens, cfg.video_tokens
         self.cfg, self.na, self.nv = cfg, na, nv
         self.rows_a, self.rows_v = na * La, nv * Lv
         self.rows = self.rows_a + self.rows_v
         self.blocks, self.final = blocks, final
         row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-        self.stack = Stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, cfg.depth, row_mod, inference=True)
+        self.stack = Stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, cfg.depth, row_mod, inference=inference,
+                           pool=pool, opts=opts)
         self.emb_a = self.emb_v = None
         if na:
             self.emb_a = PatchEmbedder(arena, dev, self.rows_a, True, cfg)

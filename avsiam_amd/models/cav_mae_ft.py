@@ -1,14 +1,25 @@
-"""``CAVMAEFT_BASE`` - the fine-tuned classifier's INFERENCE modes on the hand-written gfx950 kernels.
+"""``CAVMAEFT_BASE`` - the fine-tuned classifier on the hand-written gfx950 kernels: its inference modes, and fine-tuning.
 
 Boundary kept: the constructor and ``forward(a, v, mode, is_eval=False)`` of
 /root/reference/src/models/cav_mae_base.py:744-746,827 and the 553-key ``state_dict()`` schema (so the checkpoints the
-reference's fine-tuning writes, traintest_ft_base.py:255-264, load here, ``module.`` prefix or not), with the return
-shapes of every mode (:847,866,892,961,1035).
+reference's fine-tuning writes, traintest_ft_base.py:255-264, load here, ``module.`` prefix or not; a pre-training CAVMAE_BASE checkpoint
+loads with strict=False as run_cavmae_ft_base.py:243-249 does), with the return shapes of every mode (:847,866,892,961,1035).
 
-Scope: forward only.  Parameters are registered with ``requires_grad=False`` and outputs
-carry no autograd graph; fine-tuning (the backward of these modes, traintest_ft_base.py:143-175) is out of scope.
+Scope.  By default the model is inference-only: parameters are registered with ``requires_grad=False``, outputs carry no autograd graph,
+and only the forward buffers exist.  Fine-tuning is switched on the standard way - ``model.requires_grad_(True)``, or per parameter as
+the reference's freeze_base loop does (traintest_ft_base.py:68-71).  Then, with grad mode on and a trainable mode (``audioonly``,
+``videoonly``, ``mm_grad`` with is_eval=False; ``retrieval`` and the is_eval forms stay inference-only, as in the reference), ``forward``
+returns its outputs from ONE autograd node whose backward is the hand-scheduled reverse of ft_train.py: an output that gets no gradient
+is skipped, the encoder's backward runs only when a base parameter requires a gradient, and ``.grad`` is delivered as views of a flat
+gradient arena (allocated, with the transposed weight copies, on first training use) to exactly the parameters the reference's autograd
+would reach.  One backward per forward, and every ``.grad`` must be cleared (set to None, torch's default zero_grad) before the next
+backward: gradient accumulation across backwards is refused with an error.
+``train_step`` (traintest_ft_base.train_step) is the fused step: forward of the loss's branch only, the HIP loss kernel, the backward and
+the HIP Adam over the reference's three parameter groups, without a host sync.  The bf16 path only (fp8 fine-tuning is refused).
 There is no CPU/eager fallback: ``forward`` without a GPU and libavsiam_hip.so raises.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -19,8 +30,99 @@ from ..param_spec import build_spec_ft
 from ..weights import synth_state_ft
 from .cav_mae_base import _attach
 
+
+def _padded(info):
+    """elements a tensor occupies in the arena (ALIGN-padded)"""
+    from ..arena import ALIGN
+    return (math.prod(info.shape) + ALIGN - 1) // ALIGN * ALIGN
+
 MODES = ("audioonly", "videoonly", "retrieval", "mm_grad")
+TRAIN_MODES = ("audioonly", "videoonly", "mm_grad")
 MAX_ENGINES = 4          # (batch, frames) shapes whose activation buffers are kept resident
+MAX_TRAIN_ENGINES = 2    # ... of them with training activations
+
+
+def param_group(name):
+    """The reference's optimizer groups (traintest_ft_base.py:47-57): names containing 'mlp_head' -> "head" (lr * head_lr), 'mm_layer' ->
+    "mm" (lr * mm_lr), everything else -> "base" (lr; the group freeze_base freezes)."""
+    if "mlp_head" in name:
+        return "head"
+    if "mm_layer" in name:
+        return "mm"
+    return "base"
+
+
+def _modality(name):
+    """'a' / 'v' for base parameters only one modality's rows read (patch embeddings, positional tables, the _a / _v LayerNorms, the final
+    norms), 's' for the shared ones (cav_mae_base.py:829-841,852-860)."""
+    if any(k in name for k in ("patch_embed_a.", "pos_embed_a", "norm_a.", "norm1_a.", "norm2_a.")):
+        return "a"
+    if any(k in name for k in ("patch_embed.", "pos_embed", "vit_base.norm.", "norm1_v.", "norm2_v.")):
+        return "v"
+    return "s"
+
+
+def grad_class(name):
+    """Unit of gradient liveness: parameters of one class get a gradient in exactly the same backwards (and so share an Adam step count)."""
+    g = param_group(name)
+    if g == "head":
+        return name.split(".")[0]                       # mlp_head | mlp_head_a | mlp_head_mm | mlp_head_mm_v2
+    if g == "mm":
+        return "mm"
+    return "base_" + _modality(name)
+
+
+def live_classes(mode, live):
+    """Classes the reference's autograd reaches from the live outputs (ft_train OUT / OUT_A / OUT_V bits) of a training mode."""
+    from ..ft_train import OUT, OUT_A, OUT_V
+    if mode == "audioonly":
+        return {"base_a", "base_s", "mlp_head_a"} if live else set()
+    if mode == "videoonly":
+        return {"base_v", "base_s", "mlp_head"} if live else set()
+    out = set()
+    if live & OUT:
+        out |= {"base_a", "base_v", "base_s", "mm", "mlp_head_mm"}
+    if live & OUT_A:
+        out |= {"base_a", "base_s", "mlp_head_a"}
+    if live & OUT_V:
+        out |= {"base_v", "base_s", "mlp_head"}
+    return out
+
+
+class _FtNode(torch.autograd.Function):
+    """One node for a training forward of CAVMAEFT_BASE: forward launches the kernel schedule, backward the hand-written reverse."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, eng, mode, a, v):
+        ctx.set_materialize_grads(False)
+        from ..ft_train import OUT, OUT_A, OUT_V
+        heads = (OUT | OUT_A | OUT_V) if mode == "mm_grad" else 0
+        res = eng.forward(mode, a, v, heads)
+        ctx.model, ctx.eng, ctx.mode, ctx.token = model, eng, mode, eng.token
+        if mode == "audioonly":
+            ctx.bits = (OUT_A,)
+            return res[OUT_A].clone()
+        if mode == "videoonly":
+            ctx.bits = (OUT_V,)
+            return res[OUT_V].view(eng.B, eng.T, eng.L).squeeze(1).clone()
+        ctx.bits = (OUT, OUT_A, OUT_V)
+        return res[OUT].clone(), res[OUT_A].clone(), res[OUT_V].clone()
+
+    @staticmethod
+    def backward(ctx, *grads):
+        eng = ctx.eng
+        from ..ft_train import OUT, OUT_A, OUT_V
+        heads = {OUT: eng.head_mm, OUT_A: eng.head_a, OUT_V: eng.head_v}
+        live = 0
+        for bit, g in zip(ctx.bits, grads):
+            if g is None:
+                continue
+            live |= bit
+            h = heads[bit]
+            n = g.numel() // eng.L
+            h.dlog[:n, :eng.L].copy_(g.reshape(n, eng.L))
+        ctx.model._backward(eng, ctx.token, ctx.mode, live)
+        return (None,) * 6
 
 
 class CAVMAEFT_BASE(nn.Module):
@@ -47,7 +149,10 @@ class CAVMAEFT_BASE(nn.Module):
         for k in first + tuple(k for k in mods if k not in first):
             self._modules[k] = mods[k]
         self._engines = {}
+        self._train_engines = {}
         self._shadow_dirty = True
+        self._versions = None
+        self._opt = None                                           # HIP Adam state of train_step / adam_step
 
     def __create_fusion__(self):
         """mm_layer_1/2 <- copies of blocks 10 and 11 (:824-826; the fine-tune CLI calls it after loading a pre-trained
@@ -68,7 +173,10 @@ class CAVMAEFT_BASE(nn.Module):
             self.arena.to(probe.device)
             for name, p in self._params.items():
                 p.data = self.arena.view(name)
+                p.grad = None
             self._engines.clear()
+            self._train_engines.clear()
+            self._opt = None
             self._shadow_dirty = True
         return self
 
@@ -93,6 +201,153 @@ class CAVMAEFT_BASE(nn.Module):
             self._engines[key] = self._engines.pop(key)            # most recently used last
         return self._engines[key]
 
+    # ---- fine-tuning ---------------------------------------------------------------------------------------------
+    def _trainable(self):
+        return [n for n, p in self._params.items() if p.requires_grad]
+
+    def _train_engine(self, batch, frames):
+        if self.arena.enable_training():
+            self._shadow_dirty = True
+        key = (batch, frames)
+        if key not in self._train_engines:
+            from ..ft_train import FtTrain
+            while len(self._train_engines) >= MAX_TRAIN_ENGINES:
+                self._train_engines.pop(next(iter(self._train_engines)))
+            self._train_engines[key] = FtTrain(self.arena, self.cfg, self.label_dim, batch, frames, self.arena.p.device)
+        return self._train_engines[key]
+
+    def _sync_shadows(self):
+        # an optimizer the model does not know about (torch.optim.Adam over .grad, in-place ops on the parameters under no_grad) changes the fp32
+        # masters in place: every such op bumps the parameter's version counter, so a changed sum marks the bf16 shadows stale (checked only once
+        # training is switched on).  Edits through `p.data` do NOT show here (`.data` has a version counter of its own): call
+        # mark_weights_changed() after them, as after any write the model cannot see.
+        if self.arena.with_grads:
+            ver = sum(p._version for p in self._params.values())
+            if ver != self._versions:
+                self._versions = ver
+                self._shadow_dirty = True
+        if self._shadow_dirty:
+            self.arena.refresh_shadows(None)
+            for e in list(self._engines.values()) + list(self._train_engines.values()):
+                e.refresh_heads()
+            self._shadow_dirty = False
+            if self.arena.with_grads:
+                self._versions = sum(p._version for p in self._params.values())
+
+    def _prepare(self, a, v, mode):
+        """-> (a, v folded to [B*T, C, H, W], B, T) on the model's device, shapes checked"""
+        cfg, dev = self.cfg, self.arena.p.device
+        need_a, need_v = mode != "videoonly", mode != "audioonly"
+        B = (a if need_a else v).shape[0]
+        T = 1
+        if need_a:
+            if tuple(a.shape[1:]) != (cfg.audio_len, cfg.n_mels):
+                raise ValueError(f"a must be [B,{cfg.audio_len},{cfg.n_mels}], got {tuple(a.shape)}")
+            a = a.to(dev, torch.float32).contiguous()
+        if need_v:
+            if v.dim() != 5 or tuple(v.shape[2:]) != (cfg.in_chans, cfg.img_size, cfg.img_size) or v.shape[0] != B:
+                raise ValueError(f"v must be [B,T,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(v.shape)}")
+            T = v.shape[1]
+            v = v.to(dev, torch.float32).contiguous().view(B * T, cfg.in_chans, cfg.img_size, cfg.img_size)
+        return a, v, B, T
+
+    def _backward(self, eng, token, mode, live):
+        """Zero the gradient arena, run the reverse of the training forward `token` for the live outputs, deliver .grad.
+        Gradient accumulation across backwards is refused: the arena holds ONE backward's gradients, so every .grad must have been cleared
+        (set to None, torch's default zero_grad) since the last one - a backward would otherwise overwrite the gradients still delivered."""
+        eng.check(token)
+        held = [n for n, p in self._params.items() if p.grad is not None]
+        if held:
+            raise RuntimeError(f"CAVMAEFT_BASE: {len(held)} parameter(s) (e.g. {held[0]}) still hold .grad from an earlier backward; gradient "
+                               "accumulation across backwards is not supported - clear the gradients (optimizer.zero_grad() / model.zero_grad(), "
+                               "set_to_none=True) before the next backward")
+        trainable = set(self._trainable())
+        cls = live_classes(mode, live)
+        names = [n for n in trainable if grad_class(n) in cls and self.arena.info[n].live]
+        base = any(param_group(n) == "base" for n in names)
+        from .. import ops as _ops
+        _ops.timed("torch_zero_grads", lambda: self.arena.zero_grad_range(1))
+        eng.backward(token, live if names else 0, base=base)
+        for n in names:
+            self._params[n].grad = self.arena.gview(n)
+        return names
+
+    def train_step(self, a, v, labels, lr, ftmode="mm_grad", branch=None, loss="BCE", head_lr=1.0, mm_lr=1.0, beta1=0.95, beta2=0.999,
+                   eps=1e-8, weight_decay=5e-7):
+        """One fused fine-tuning step (traintest_ft_base.py:133-175 without the host): the forward of the loss's branch only, the HIP
+        classification loss, the backward and the HIP Adam of the reference's three groups.  -> the loss (device tensor [1], no sync).
+        branch (mm_grad only): "mm" (loss on out), "a" (out_a: the audio encoder alone), "v" (out_v: the frame encoder alone)."""
+        from .. import ops
+        from ..ft_train import OUT, OUT_A, OUT_V
+        if ftmode not in TRAIN_MODES:
+            raise ValueError(f"ftmode {ftmode!r} has no training form ({', '.join(TRAIN_MODES)})")
+        if loss not in ("BCE", "CE"):
+            raise ValueError(f"loss must be BCE or CE, not {loss!r}")
+        if not self.arena.p.is_cuda:
+            raise _lib.AvsiamHipError("CAVMAEFT_BASE.train_step needs a GPU (no CPU/eager fallback). Move the model with .cuda() first.")
+        _lib.load()
+        if ftmode == "mm_grad":
+            branch = "mm" if branch is None else branch
+            if branch not in ("mm", "a", "v"):
+                raise ValueError(f"branch must be mm, a or v, not {branch!r}")
+            mode, bit = {"mm": ("mm_grad", OUT), "a": ("mm_a", OUT_A), "v": ("mm_v", OUT_V)}[branch]
+            cls_mode = {"mm": "mm_grad", "a": "audioonly", "v": "videoonly"}[branch]
+        else:
+            mode, cls_mode, bit = ftmode, ftmode, (OUT_A if ftmode == "audioonly" else OUT_V)
+        for p in self._params.values():                           # the step owns the gradients: optimizer.zero_grad() of :168
+            p.grad = None
+        a, v, B, T = self._prepare(a, v, "mm_grad" if mode == "mm_grad" else cls_mode)
+        eng = self._train_engine(B, T)
+        self._sync_shadows()
+        res = eng.forward(mode, a, v, bit)
+        head = {OUT: eng.head_mm, OUT_A: eng.head_a, OUT_V: eng.head_v}[bit]
+        x = res[bit]
+        n = x.shape[0]
+        y = labels.to(x.device, torch.float32).reshape(n, self.label_dim).contiguous()
+        if not hasattr(eng, "loss_buf") or eng.loss_buf[0].numel() < n:
+            eng.loss_buf = (torch.zeros(max(n, B * T), dtype=torch.float32, device=x.device), torch.zeros(1, dtype=torch.float32, device=x.device))
+        rows, out = eng.loss_buf
+        ops.cls_loss(x, y, n, self.label_dim, ops.CLS_BCE if loss == "BCE" else ops.CLS_CE, rows, out, dx=head.dlog)
+        names = self._backward(eng, eng.token, cls_mode if mode != "mm_grad" else "mm_grad", bit if mode == "mm_grad" else (OUT_A if cls_mode == "audioonly" else OUT_V))
+        self.adam_step(lr, head_lr, mm_lr, names, beta1, beta2, eps, weight_decay)
+        return out.clone()
+
+    def adam_step(self, lr, head_lr=1.0, mm_lr=1.0, names=None, beta1=0.95, beta2=0.999, eps=1e-8, weight_decay=5e-7):
+        """torch.optim.Adam([base lr | mlp_head* lr * head_lr | mm_layer* lr * mm_lr], weight_decay=5e-7, betas=(0.95, 0.999)) of
+        traintest_ft_base.py:78-83 over the gradients of the last backward (`names`: the parameters that got one; default: every trainable
+        parameter whose .grad is set).  Parameters without a gradient are untouched and, as in torch, keep their own step count: one count
+        per gradient class (grad_class), one launch per contiguous run of the arena."""
+        from .. import ops
+        a = self.arena
+        if names is None:
+            names = [n for n in self._trainable() if self._params[n].grad is not None and a.info[n].live]
+        if not names:
+            return
+        lo0, hi0 = a.range[1]
+        if self._opt is None:
+            self._opt = {"m": torch.zeros(hi0 - lo0, device=a.p.device), "v": torch.zeros(hi0 - lo0, device=a.p.device), "step": {}}
+        st = self._opt
+        classes = {grad_class(n) for n in names}
+        for c in classes:
+            st["step"][c] = st["step"].get(c, 0) + 1
+        mult = {"base": 1.0, "head": head_lr, "mm": mm_lr}
+        spans = sorted((a.offset[n], a.offset[n] + _padded(a.info[n]),
+                        lr * mult[param_group(n)], st["step"][grad_class(n)]) for n in names)
+        runs = []
+        for lo, hi, l, k in spans:
+            if runs and runs[-1][1] == lo and runs[-1][2] == l and runs[-1][3] == k:
+                runs[-1][1] = hi
+            else:
+                runs.append([lo, hi, l, k])
+        for lo, hi, l, k in runs:
+            ops.adam(a.p[lo:hi], a.g[lo:hi], st["m"][lo - lo0:hi - lo0], st["v"][lo - lo0:hi - lo0], a.pb[lo:hi], hi - lo, l, k, beta1, beta2, eps,
+                     weight_decay)
+        a.refresh_shadows(None, cast=False)
+        for e in list(self._engines.values()) + list(self._train_engines.values()):
+            e.refresh_heads()
+        if a.with_grads:
+            self._versions = sum(p._version for p in self._params.values())
+
     def forward(self, a, v, mode, is_eval=False):
         """a: [B, 1024, 128] fbank; v: [B, T, 3, 224, 224] frames (either may be None when the mode ignores it).
         Returns what the reference returns for the mode; any other mode returns None as there (no else branch)."""
@@ -102,6 +357,13 @@ class CAVMAEFT_BASE(nn.Module):
             raise _lib.AvsiamHipError("CAVMAEFT_BASE.forward needs a GPU: the path runs only on libavsiam_hip.so "
                                       "(no CPU/eager fallback). Move the model with .cuda() first.")
         _lib.load()
+        if torch.is_grad_enabled() and mode in TRAIN_MODES and not is_eval:        # every is_eval form stays inference-only
+            trainable = self._trainable()
+            if trainable:
+                a, v, B, T = self._prepare(a, v, mode)
+                eng = self._train_engine(B, T)
+                self._sync_shadows()
+                return _FtNode.apply(self._params[trainable[0]], self, eng, mode, a, v)
         cfg, dev = self.cfg, self.arena.p.device
         need_a, need_v = mode != "videoonly", mode != "audioonly"
         B = (a if need_a else v).shape[0]
@@ -116,11 +378,8 @@ class CAVMAEFT_BASE(nn.Module):
             T = v.shape[1]
             v = v.to(dev, torch.float32).contiguous().view(B * T, cfg.in_chans, cfg.img_size, cfg.img_size)
         eng = self._engine(B, T)
-        if self._shadow_dirty:
-            self.arena.refresh_shadows(None)
-            for e in self._engines.values():
-                e.refresh_heads()
-            self._shadow_dirty = False
+        if self._shadow_dirty or self.arena.with_grads:
+            self._sync_shadows()
         if mode == "audioonly":
             out = eng.audioonly(a).clone()
             return out.unsqueeze(1) if is_eval else out                                    # :845-847

@@ -806,6 +806,28 @@ def segment_mean_bwd(dreps, seg_start, dy, nseg, scale=1.0, row_map=None, max_ro
     _call("avs_segment_mean_bwd", dreps, seg_start, dy, nseg, dy.shape[1], float(scale), row_map, _stream())
 
 
+def segment_mean_bwd_acc(dreps, seg_start, dy, nseg, scale=1.0, row_map=None, max_row=None, accumulate=True):
+    """segment_mean_bwd that ADDS to dy (accumulate=True): the pooled heads' gradient on token rows another branch already wrote"""
+    _chk(dy, F32, "segmeanba.dy", 2); _chk(seg_start, I32, "segmeanba.seg"); _chk(dreps, F32, "segmeanba.dreps", 2); _chk(row_map, I32, "segmeanba.map")
+    assert seg_start.numel() >= nseg + 1 and dreps.shape[0] >= (nseg if row_map is None else max_row) and dreps.shape[1] == dy.shape[1]
+    assert row_map is None or (row_map.numel() >= nseg and max_row is not None)
+    _call("avs_segment_mean_bwd_acc", dreps, seg_start, dy, nseg, dy.shape[1], float(scale), row_map, int(bool(accumulate)), _stream())
+
+
+CLS_BCE, CLS_CE = 0, 1
+
+
+def cls_loss(x, y, n, L, kind, row_loss, loss, dx=None, gout=None, weight=1.0):
+    """BCE-with-logits (kind CLS_BCE) / cross-entropy with probability targets (CLS_CE) of logits x [>= n, >= L] (row-major, a column range of a
+    padded buffer is fine) against targets y [n, L]: loss[0] = weight * mean loss, dx [n, >= L] = gout[0] * weight * d(mean)/dx (gout None: 1)"""
+    for t, nm in ((x, "x"), (y, "y"), (dx, "dx")):
+        if t is not None and not (t.is_cuda and t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= n and t.shape[1] >= L):
+            raise _lib.AvsiamHipError(f"cls_loss.{nm}: need a row-major fp32 GPU matrix of at least [{n}, {L}]")
+    _chk(row_loss, F32, "cls_loss.row_loss"); _chk(loss, F32, "cls_loss.loss"); _chk(gout, F32, "cls_loss.gout")
+    assert kind in (CLS_BCE, CLS_CE) and row_loss.numel() >= n and loss.numel() >= 1
+    _call("avs_cls_loss", x, x.stride(0), y, y.stride(0), n, L, kind, gout, float(weight), row_loss, loss, dx, dx.stride(0) if dx is not None else 0, _stream())
+
+
 def mae_loss_fwd(pred, inp, mask, row_loss, loss, audio, L, nmask, total=None, total_init=True, xf=None, stride=16, row_id=None, id_base=0):
     """row_id / id_base (compact predictions: only the scored rows exist): prediction row r scores the (sample, token) row_id[r] - id_base of mask"""
     _chk(row_id, I32, "mae.row_id")

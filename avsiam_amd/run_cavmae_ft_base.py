@@ -1,0 +1,120 @@
+"""Fine-tuning entry point with the flag surface of the reference (src/run_cavmae_ft_base.py:63-139).
+
+    python -m avsiam_amd.run_cavmae_ft_base --model cav-mae-ft --ftmode mm_grad --n_class 527 --loss BCE --lr 1e-4 --head_lr 100 \\
+        --mm_lr 100 --batch_size 8 --n_epochs 15 --pretrain_path exp/models/audio_model.20.pth --exp_dir ./ft_base ...
+
+Data flags behave as in the pre-training entry point: --data_train '' or 'synthetic' gives AudioSet-shaped synthetic clips with
+label-smoothed multi-hot labels (the json/wav/mp4 pipeline is out of scope on this path).  --pretrain_path loads a CAVMAE_BASE checkpoint
+(with or without the 'module.' prefix) with strict=False (:243-249).  Accepted but not implemented: the augmentation flags (freqm, timem,
+noise, mixup), --wa (weight averaging) and --bal - a warning names each one set to a non-default value; --warmup, distillation weights and
+logging are inert.  Data-parallel runs (world size > 1) are refused.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
+Extensions: --steps-per-epoch / --val-steps (synthetic epoch lengths).
+"""
+import argparse
+import ast
+import os
+
+
+def build_parser():
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("--data_train", type=str, default='', help="training data json ('' or 'synthetic': synthetic tensors)")
+    p.add_argument("--data_val", type=str, default='', help="validation data json ('' or 'synthetic')")
+    p.add_argument("--data_eval", type=str, default=None)
+    p.add_argument("--label_csv", type=str, default='')
+    p.add_argument("--n_class", type=int, default=527)
+    p.add_argument("--model", type=str, default='cav-mae-ft', choices=["cav-mae-ft"])
+    p.add_argument("--dataset", type=str, default="audioset")
+    p.add_argument("--dataset_mean", type=float, default=-5.081)
+    p.add_argument("--dataset_std", type=float, default=4.4849)
+    p.add_argument("--target_length", type=int, default=1024)
+    p.add_argument("--noise", type=ast.literal_eval, default=False)
+    p.add_argument("--exp_dir", type=str, default="")
+    p.add_argument('--lr', '--learning-rate', default=0.001, type=float)
+    p.add_argument("--optim", type=str, default="adam", choices=["sgd", "adam"])
+    p.add_argument('-b', '--batch_size', default=48, type=int)
+    p.add_argument('-w', '--num_workers', default=32, type=int)
+    p.add_argument("--n_epochs", type=int, default=10)
+    p.add_argument("--lr_patience", type=int, default=1)
+    p.add_argument("--lr_adapt", type=ast.literal_eval, default=False)
+    p.add_argument("--metrics", type=str, default="mAP", choices=["mAP", "acc"])
+    p.add_argument("--loss", type=str, default="BCE", choices=["BCE", "CE"])
+    p.add_argument('--warmup', type=ast.literal_eval, default='True')
+    p.add_argument("--lrscheduler_start", default=2, type=int)
+    p.add_argument("--lrscheduler_step", default=1, type=int)
+    p.add_argument("--lrscheduler_decay", default=0.5, type=float)
+    p.add_argument('--freqm', type=int, default=0)
+    p.add_argument('--timem', type=int, default=0)
+    p.add_argument("--wa", type=ast.literal_eval, default=False)
+    p.add_argument("--wa_start", type=int, default=1)
+    p.add_argument("--wa_end", type=int, default=10)
+    p.add_argument("--n-print-steps", dest="n_print_steps", type=int, default=100)
+    p.add_argument('--save_model', type=ast.literal_eval, default=False)
+    p.add_argument("--mixup", type=float, default=0)
+    p.add_argument("--bal", type=str, default=None)
+    p.add_argument("--label_smooth", type=float, default=0.1)
+    p.add_argument("--weight_file", type=str, default=None)
+    p.add_argument("--pretrain_path", type=str, default='None')
+    p.add_argument("--ftmode", type=str, default='multimodal')
+    p.add_argument("--ftmode_test", type=str, default=None)
+    p.add_argument("--head_lr", type=float, default=50.0)
+    p.add_argument("--mm_lr", type=float, default=None)
+    p.add_argument('--freeze_base', type=ast.literal_eval, default=False)
+    p.add_argument('--skip_frame_agg', type=ast.literal_eval, default=False)
+    p.add_argument("--dis_w", type=float, default=0)
+    p.add_argument("--dis_w_2", type=float, default=0)
+    p.add_argument("--master_addr", type=str)
+    p.add_argument("--nproc_per_node", type=int)
+    p.add_argument("--wandb", type=int, default=0)
+    p.add_argument('--model_name', type=str, default=None)
+    p.add_argument('--world_size', default=1, type=int)
+    p.add_argument('--local_rank', default=-1, type=int)
+    p.add_argument('--dist_url', default='env://')
+    p.add_argument('--steps-per-epoch', dest="steps_per_epoch", default=20, type=int, help="synthetic-data epoch length")
+    p.add_argument('--val-steps', dest="val_steps", default=2, type=int, help="synthetic validation batches per epoch")
+    return p
+
+
+def load_pretrained(model, path):
+    """run_cavmae_ft_base.py:243-249: strict=False load of a (pre-training or fine-tuning) checkpoint -> (missing, unexpected)"""
+    import torch
+    sd = torch.load(path, map_location="cpu")
+    miss, unexpected = model.load_state_dict(sd, strict=False)
+    print("now load cav-mae pretrained weights from ", path)
+    print("Missing: ", miss)
+    print("Unexpected: ", unexpected)
+    return miss, unexpected
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    world = int(os.environ.get("WORLD_SIZE", args.world_size))
+    if world > 1:
+        raise SystemExit("data-parallel fine-tuning (DDP over RCCL) is not implemented on this path: run one process")
+    if args.data_train not in ('', 'synthetic') or args.data_val not in ('', 'synthetic'):
+        raise SystemExit("only synthetic AudioSet-shaped data is supported on this path (see module docstring)")
+    if args.ftmode not in ("audioonly", "videoonly", "mm_grad"):
+        raise SystemExit(f"--ftmode {args.ftmode}: the trainable modes are audioonly, videoonly and mm_grad")
+    inert = [f"--{k} {getattr(args, k)}" for k, off in (("mixup", 0), ("wa", False), ("freqm", 0), ("timem", 0), ("noise", False), ("bal", None))
+             if getattr(args, k) not in (off, 'None')]
+    if inert:
+        print("WARNING: not implemented on this path, ignored: " + ", ".join(inert) + " - this run trains without them", flush=True)
+    from .config import AVSiamConfig
+    from .models import CAVMAEFT_BASE
+    from .traintest_ft_base import SyntheticFtLoader, train
+    cfg = AVSiamConfig()
+    model = CAVMAEFT_BASE(label_dim=args.n_class)
+    if args.pretrain_path != 'None':
+        load_pretrained(model, args.pretrain_path)
+    model = model.cuda()
+    dev = model.arena.p.device
+    train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87, label_smooth=args.label_smooth)
+    val_frames = 10 if (args.ftmode_test or args.ftmode) == "mm_grad" else 1          # validate() runs is_eval=True: mm_grad wants 10 frames
+    val_loader = SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88, label_smooth=args.label_smooth,
+                                   frames=val_frames)
+    os.makedirs(args.exp_dir or ".", exist_ok=True)
+    args.exp_dir = args.exp_dir or "."
+    return train(model, train_loader, val_loader, None, args)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,194 @@
+"""Fine-tuning loop of the reference (src/traintest_ft_base.py) on the HIP path.
+
+``train_step`` is the fused step (forward of the loss's branch, the HIP classification loss, the hand-scheduled backward and the HIP Adam of
+the three parameter groups, no host sync); ``train`` / ``validate`` keep the reference's signatures and returns, branch draw (:133-160), losses
+(:105-110), schedulers (:91-97), freeze_base (:68-71) and artefacts (models/audio_model.{epoch}.pth, best_audio_model.pth, result.csv).
+Deliberate differences: the reference's stray forward outside autocast (:143, which would also break every mode but mm_grad) is not
+reproduced; metrics (mAP, mAUC, acc) are computed in numpy; data-parallel fine-tuning, weight averaging (--wa) and mixup are not implemented.
+"""
+import os
+import random
+import time
+
+import numpy as np
+import torch
+
+from .models.cav_mae_ft import param_group
+
+
+def draw_branch(prob):
+    """traintest_ft_base.py:153-160: prob > 0.5 -> loss on out, prob < 0.25 -> out_a, otherwise out_v"""
+    if prob > 0.5:
+        return "mm"
+    if prob < 0.25:
+        return "a"
+    return "v"
+
+
+def train_step(model, a, v, labels, lr, ftmode, branch=None, loss="BCE", head_lr=50.0, mm_lr=None):
+    """One fused step; -> the loss (device tensor [1]).  mm_lr None -> head_lr, as the reference's default --mm_lr None would fail
+    (lr * None) and every launcher passes it."""
+    return model.train_step(a, v, labels, lr, ftmode, branch=branch, loss=loss, head_lr=head_lr, mm_lr=head_lr if mm_lr is None else mm_lr)
+
+
+def apply_freeze_base(model, freeze):
+    for name, p in model.named_parameters():
+        p.requires_grad_(not (freeze and param_group(name) == "base"))
+
+
+# ---- metrics (numpy; the reference's utilities.calculate_stats uses sklearn) -----------------------------------------------
+def _average_precision(y, s):
+    order = np.argsort(-s, kind="stable")
+    y = y[order]
+    npos = y.sum()
+    if npos == 0:
+        return np.nan
+    hits = np.cumsum(y)
+    prec = hits / np.arange(1, len(y) + 1)
+    return float((prec * y).sum() / npos)
+
+
+def _auc(y, s):
+    npos, nneg = y.sum(), len(y) - y.sum()
+    if npos == 0 or nneg == 0:
+        return np.nan
+    order = np.argsort(s, kind="stable")
+    ranks = np.empty(len(s))
+    ss = s[order]
+    i = 0
+    while i < len(ss):                                    # average ranks of ties
+        j = i
+        while j + 1 < len(ss) and ss[j + 1] == ss[i]:
+            j += 1
+        ranks[order[i:j + 1]] = (i + j) / 2 + 1
+        i = j + 1
+    return float((ranks[y > 0].sum() - npos * (npos + 1) / 2) / (npos * nneg))
+
+
+def calculate_stats(output, target):
+    """Per class {'AP', 'auc', 'acc'} as the reference's utilities.stats.calculate_stats (acc: top-1 of the argmaxes, class-independent)."""
+    target = (np.asarray(target) > 0.5).astype(np.float64)
+    output = np.asarray(output, dtype=np.float64)
+    acc = float(np.mean(np.argmax(target, 1) == np.argmax(output, 1)))
+    return [{"AP": _average_precision(target[:, k], output[:, k]), "auc": _auc(target[:, k], output[:, k]), "acc": acc}
+            for k in range(target.shape[1])]
+
+
+def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
+    """validate of the reference (:292-350): no-grad forward in args.ftmode_test with is_eval=True (mm_grad: one joint logit row per frame of
+    10-frame clips), loss = args.loss on the mean over dim 1 per batch, sigmoid of the outputs, stats of their mean over dim 1.
+    -> (stats, loss), or (stats, sigmoid outputs, targets) with output_pred - as the reference.
+    Differences, deliberate: args.ftmode_test None (the launchers do not pass it; the reference would then select no mode and fail) falls back to
+    args.ftmode; a two-dimensional output (videoonly with one frame squeezes its frame axis, :865) gets that axis back before the mean, where
+    the reference would average over the classes; one process only (no distributed_concat)."""
+    device = audio_model.arena.p.device
+    mode = getattr(args, "ftmode_test", None) or args.ftmode
+    loss_fn = torch.nn.BCEWithLogitsLoss() if args.loss == "BCE" else torch.nn.CrossEntropyLoss()
+    outs, tgts, losses = [], [], []
+    with torch.no_grad():
+        for a_input, v_input, labels in val_loader:
+            out = audio_model(a_input.to(device), v_input.to(device), mode, is_eval=True)
+            if out.dim() == 2:
+                out = out.unsqueeze(1)
+            labels = labels.to(device)
+            losses.append(loss_fn(out.mean(dim=1), labels))
+            outs.append(out)
+            tgts.append(labels)
+    loss = float(torch.stack(losses).mean()) if losses else float("nan")
+    audio_output = torch.sigmoid(torch.cat(outs).float())
+    target = torch.cat(tgts).float()
+    stats = calculate_stats(audio_output.mean(dim=1).cpu().numpy(), target.cpu().numpy())
+    if output_pred:
+        return stats, audio_output, target
+    return stats, loss
+
+
+class SyntheticFtLoader:
+    """AudioSet-shaped synthetic clips (no dataset here): a ~ N(0,1) [B, target_length, 128], v ~ N(0,1) [B, frames, 3, 224, 224] and
+    label-smoothed multi-hot labels (dataloader.py: 1 - label_smooth on the positives, label_smooth / n_class elsewhere)."""
+
+    def __init__(self, cfg, batch_size, steps, n_class, device, seed=87, label_smooth=0.1, frames=1):
+        import dataclasses
+        from .weights import synth_inputs
+        a, v = synth_inputs(dataclasses.replace(cfg, frames=frames), batch_size, seed)
+        g = torch.Generator().manual_seed(seed)
+        hot = (torch.rand(batch_size, n_class, generator=g) < 0.02).float()
+        hot[torch.arange(batch_size), torch.randint(0, n_class, (batch_size,), generator=g)] = 1.0
+        y = hot * (1.0 - label_smooth) + label_smooth / n_class
+        self.a, self.v, self.y, self.steps = a.to(device), (v.unsqueeze(1) if frames == 1 else v).to(device), y.to(device), steps
+
+    def __len__(self):
+        return self.steps
+
+    def __iter__(self):
+        for _ in range(self.steps):
+            yield self.a, self.v, self.y
+
+
+class _LrHolder:
+    """The parameter groups the reference's schedulers drive (base, mlp, mm: :78-83); train_step reads the three rates back."""
+
+    def __init__(self, lr, head_lr, mm_lr):
+        self._p = torch.nn.Parameter(torch.zeros(1))
+        self.opt = torch.optim.SGD([{"params": [self._p], "lr": lr}, {"params": [torch.nn.Parameter(torch.zeros(1))], "lr": lr * head_lr},
+                                    {"params": [torch.nn.Parameter(torch.zeros(1))], "lr": lr * mm_lr}], lr=lr)
+
+    def rates(self):
+        base, head, mm = (g["lr"] for g in self.opt.param_groups)
+        return base, head / base if base else 0.0, mm / base if base else 0.0
+
+
+def train(audio_model, train_loader, test_loader, test_sampler, args):
+    """train of the reference (:29-290) with the fused step.  args: ftmode, loss, lr, head_lr, mm_lr, freeze_base, n_epochs, lr_adapt,
+    lr_patience, lrscheduler_start / _step / _decay, metrics, exp_dir, save_model, n_print_steps."""
+    if getattr(args, "world_size", 1) > 1:
+        raise SystemExit("data-parallel fine-tuning is not implemented on this path (run one process)")
+    exp_dir = args.exp_dir
+    os.makedirs(os.path.join(exp_dir, "models"), exist_ok=True)
+    apply_freeze_base(audio_model, bool(getattr(args, "freeze_base", False)))
+    mm_lr = args.mm_lr if getattr(args, "mm_lr", None) is not None else args.head_lr
+    hold = _LrHolder(args.lr, args.head_lr, mm_lr)
+    if getattr(args, "lr_adapt", False):
+        scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(hold.opt, mode="max", factor=0.5, patience=args.lr_patience)
+    else:
+        scheduler = torch.optim.lr_scheduler.MultiStepLR(hold.opt, list(range(args.lrscheduler_start, 1000, args.lrscheduler_step)),
+                                                         gamma=args.lrscheduler_decay)
+    main_metrics = getattr(args, "metrics", "mAP")
+    best_mAP, best_acc, best_epoch = -np.inf, -np.inf, 0
+    result = np.zeros([args.n_epochs, 4])
+    global_step = 0
+    for epoch in range(1, args.n_epochs + 1):
+        t0 = time.time()
+        losses = []
+        base_lr, head_lr, mm_ratio = hold.rates()
+        for a_input, v_input, labels in train_loader:
+            prob = random.uniform(0, 1)
+            branch = draw_branch(prob) if args.ftmode == "mm_grad" else None
+            losses.append(audio_model.train_step(a_input, v_input, labels, base_lr, args.ftmode, branch=branch, loss=args.loss,
+                                                 head_lr=head_lr, mm_lr=mm_ratio))
+            global_step += 1
+            if global_step % args.n_print_steps == 0:
+                print(f"Epoch: [{epoch}][{global_step}] train loss {float(losses[-1]):.5f}", flush=True)
+        train_loss = float(torch.stack(losses).mean()) if losses else float("nan")
+        stats, valid_loss = validate(audio_model, test_loader, test_sampler, args)
+        mAP = float(np.nanmean([s["AP"] for s in stats]))
+        mAUC = float(np.nanmean([s["auc"] for s in stats]))
+        acc = stats[0]["acc"]
+        result[epoch - 1, :] = [acc if main_metrics == "acc" else mAP, mAUC, base_lr, train_loss]
+        np.savetxt(os.path.join(exp_dir, "result.csv"), result, delimiter=",")
+        print(f"epoch {epoch}: mAP {mAP:.6f} mAUC {mAUC:.6f} acc {acc:.6f} train loss {train_loss:.6f} valid loss {valid_loss:.6f} "
+              f"({time.time() - t0:.1f}s)", flush=True)
+        better = mAP > best_mAP if main_metrics == "mAP" else acc > best_acc
+        best_mAP, best_acc = max(best_mAP, mAP), max(best_acc, acc)
+        sd = {"module." + k: t.detach().cpu() for k, t in audio_model.state_dict().items()}
+        if better:
+            best_epoch = epoch
+            torch.save(sd, os.path.join(exp_dir, "models", "best_audio_model.pth"))
+        if getattr(args, "save_model", False):
+            torch.save(sd, os.path.join(exp_dir, "models", f"audio_model.{epoch}.pth"))
+        hold.opt.step()                                   # (no gradients: a no-op that keeps the scheduler's step order)
+        if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
+            scheduler.step(mAP if main_metrics == "mAP" else acc)
+        else:
+            scheduler.step()
+    return {"best_epoch": best_epoch, "best_mAP": best_mAP, "best_acc": best_acc, "result": result}

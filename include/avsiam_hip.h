@@ -69,7 +69,11 @@ int avs_layernorm_fwd_q8(const float* x, const float* g0, const float* b0, const
  * dres_bf16 != 0: dres is bf16 (the residual-gradient stream kept in bf16 between blocks - the previous call's dx_bf16);
  * dx may then be NULL (only dx_bf16 is written); dx_bf16 must not alias a bf16 dres.
  * dx8 / q8 (fp8 backward; both or neither): also dx8 = e5m2(clamp(dx * q8[0])) - the gradient operand of an fp8 input-gradient GEMM -
- * with max |dx| folded into the device record q8 (avs_fp8_scale_update) */
+ * with max |dx| folded into the device record q8 (avs_fp8_scale_update)
+ * D = 1536 / 2048 / 2560: the fusion classification head's LayerNorm over the concatenated audio | video feature (mlp_head_mm[0],
+ * src/models/cav_mae_base.py:812-813,1031, and its backward at traintest_ft_base.py:171): few rows, dx / dx_bf16 / dres / row_mod / out_map as
+ * above, dg / db reduced in the call in row order (one writer per element; a NULL target skips it), ws unused, no dx8 and no dcol.  These
+ * widths came with avs_cls_loss (ABI version unchanged: additions only): a library that exports avs_cls_loss accepts them */
 int avs_layernorm_bwd(const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd, const float* g0,
                       const float* g1, const uint8_t* row_mod, const int* out_map, const void* dres, int dres_bf16, float* dx,
                       avs_bf16* dx_bf16, float* dg0, float* db0, float* dg1, float* db1, float* dcol, float* ws, int rows,
@@ -323,6 +327,10 @@ int avs_unshuffle_bwd_map(const float* dout, const int* src_row, int B, int T, i
 int avs_segment_mean_fwd(const float* y, const int* seg_start, float* reps, int nseg, int D, const int* row_map, avs_stream_t stream);
 int avs_segment_mean_bwd(const float* dreps, const int* seg_start, float* dy, int nseg, int D, float scale, const int* row_map,
                          avs_stream_t stream);
+/* the same with accumulate != 0: dy[r] += ... (the fine-tuned model's pooled heads out_a / out_v, cav_mae_base.py:1011-1012, add their
+ * gradient to what the fusion blocks' backward left on the same token rows, :1014-1023).  A segment's rows have one writer: no atomics */
+int avs_segment_mean_bwd_acc(const float* dreps, const int* seg_start, float* dy, int nseg, int D, float scale, const int* row_map,
+                             int accumulate, avs_stream_t stream);
 
 /* ---- masked-MSE with patchify on the fly (patchify + forward_mae_loss, cav_mae_base.py:343-351,663-683) */
 /* loss[0] = masked mean; total (may be NULL): total[0] = (total_init ? 0 : total[0]) + loss[0]  (loss_mae = a + v, :707) */
@@ -368,6 +376,15 @@ int avs_gemm_f32_small(const float* A, long long sam, long long sak, const float
 int avs_infonce_fwd(const float* total, float* stats, float* out, int N, float weight, avs_stream_t stream);
 int avs_infonce_dlogits(const float* total, const float* stats, const float* gout, float weight, float* dtotal, int N,
                         avs_stream_t stream);
+
+/* ---- classification loss of the fine-tuning loop (src/traintest_ft_base.py:105-110 loss_fn, :156-160 applied to out / out_a / out_v, the
+ * backward of :171).  logits x [n, L] (row stride ldx: the head's output buffer is padded), targets y [n, L] (ldy).
+ * kind 0: nn.BCEWithLogitsLoss() - mean over n * L of max(x,0) - x y + log1p(exp(-|x|)), d/dx = (sigmoid(x) - y) / (n L)
+ * kind 1: nn.CrossEntropyLoss() with probability targets - mean over n of sum_j y_j (logsumexp(x) - x_j), d/dx = (softmax(x) sum_j y_j - y) / n
+ * loss[0] = weight * mean loss (device scalar, no host sync): per-row sums into row_loss [n], then ONE ordered single-block sum (no float
+ * atomics: the same bits every run).  dx (may be NULL) [n, L] (ldd) = gout[0] * weight * d(mean loss)/dx; gout (device, may be NULL = 1). */
+int avs_cls_loss(const float* x, long long ldx, const float* y, long long ldy, int n, int L, int kind, const float* gout, float weight,
+                 float* row_loss, float* loss, float* dx, long long ldd, avs_stream_t stream);
 
 /* ---- weights: bf16 shadow copies and the fused Adam step (torch.optim.Adam as built at
  * src/traintest_cavmae_base.py:64-66) */
