@@ -22,11 +22,11 @@ class AvsiamHipError(RuntimeError):
 
 
 def parse_header(path=HEADER):
-    """-> {name: (restype, [argtype, ...])} as strings 'ptr' | 'int' | 'll' | 'float' | 'str'."""
+    """-> {name: (restype, [argtype, ...])} as strings 'ptr' | 'int' | 'll' | 'ull' | 'size' | 'float' | 'str'."""
     src = open(path).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     protos = {}
-    for m in re.finditer(r"(const\s+char\s*\*|long\s+long|int)\s+(avs_\w+)\s*\(([^)]*)\)\s*;", src):
+    for m in re.finditer(r"(const\s+char\s*\*|long\s+long|size_t|int)\s+(avs_\w+)\s*\(([^)]*)\)\s*;", src):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
         kinds = []
         if args and args != "void":
@@ -38,17 +38,19 @@ def parse_header(path=HEADER):
                     kinds.append("ull")
                 elif a.startswith("long long"):
                     kinds.append("ll")
+                elif a.startswith("size_t"):
+                    kinds.append("size")
                 elif a.startswith("float"):
                     kinds.append("float")
                 elif a.startswith("int"):
                     kinds.append("int")
                 else:
                     raise ValueError(f"unparsed argument '{a}' of {name}")
-        protos[name] = ("str" if "char" in ret else "ll" if "long" in ret else "int", kinds)
+        protos[name] = ("str" if "char" in ret else "ll" if "long" in ret else "size" if "size_t" in ret else "int", kinds)
     return protos
 
 
-_CT = {"ptr": ctypes.c_void_p, "int": ctypes.c_int, "ll": ctypes.c_longlong, "ull": ctypes.c_ulonglong, "float": ctypes.c_float}
+_CT = {"ptr": ctypes.c_void_p, "int": ctypes.c_int, "ll": ctypes.c_longlong, "ull": ctypes.c_ulonglong, "size": ctypes.c_size_t, "float": ctypes.c_float}
 
 
 def load():
@@ -62,7 +64,7 @@ def load():
     _protos = parse_header()
     for name, (ret, kinds) in _protos.items():
         fn = getattr(lib, name)
-        fn.restype = ctypes.c_char_p if ret == "str" else ctypes.c_longlong if ret == "ll" else ctypes.c_int
+        fn.restype = ctypes.c_char_p if ret == "str" else ctypes.c_longlong if ret == "ll" else ctypes.c_size_t if ret == "size" else ctypes.c_int
         fn.argtypes = [_CT[k] for k in kinds]
     # the library never reads the environment (include/avsiam_hip.h): the AVSIAM_* tuning variables are applied HERE, once - and BEFORE the
     # library is published, so that a rejected value fails every load() the same way instead of leaving a half-configured library behind
@@ -88,7 +90,7 @@ def env_value(name):
 
 _ENV_KNOBS = {"AVSIAM_GEMM_TILE": "gemm_tile", "AVSIAM_GEMM_NT8": "gemm_nt8", "AVSIAM_NT_TILE_H": "nt_tile_h", "AVSIAM_NT_GRID": "nt_grid",
               "AVSIAM_CU_RESERVE": "cu_reserve", "AVSIAM_LN_DMA": "ln_dma", "AVSIAM_LN_RPW": "ln_rpw", "AVSIAM_ATTN_RING": "attn_ring", "AVSIAM_GEMM_RING": "gemm_ring",
-              "AVSIAM_NT_BIG_MIN": "nt_big_min", "AVSIAM_DET": "det"}
+              "AVSIAM_NT_BIG_MIN": "nt_big_min", "AVSIAM_DET": "det", "AVSIAM_RETR_SEGMENTS": "retr_segments"}
 
 
 def tuning_set(name, value):

@@ -153,6 +153,8 @@ struct AvsTuning {
                            // not split their token rows (one workgroup per output tile), column sums / the vector-matrix product / the LayerNorm slab
                            // reduce run as one block per column group, the positional-embedding scatter and the un-shuffle's token sums take their
                            // atomics-free forms: two runs of a step give the same bits (debugging; slower).  0 (default)        AVSIAM_DET
+    int retr_segments;     // avs_retrieval_rank: gallery-column segments per 128-row query panel: 0 (default) automatic - panels x segments
+                           // >= 2 x CUs where the gallery has that many tiles, one segment at gallery sizes | 1..64 forced (tests: every value gives the same bytes)
 };
 AvsTuning& avs_tuning();
 extern "C" int avs_tuning_set(const char* name, int value);

@@ -141,6 +141,29 @@ class FtForward:
         v = enc.yf[enc.rows_a:enc.rows].view(self.B, self.T, cfg.video_tokens, cfg.embed_dim)
         return a, v[:, frame_index]
 
+    def retrieval_feats(self, audio, frames, out_a, out_v, frame_index=5):
+        """Clip-level retrieval features (src/retrieval.py:70-78: token mean, then L2 normalisation, of what `retrieval` returns) ->
+        out_a / out_v: fp32 [B, D] unit vectors, written in place (slices of the caller's dataset-level buffers: nothing is copied or
+        synchronised per batch).  Frames are independent sequences of the encoder (`rearrange(v, 'b t c w h -> (b t) c w h')`,
+        cav_mae_base.py:901-920), so only frame `frame_index` of every clip is embedded - the patch gather reads image b * T + frame_index
+        of the folded [B * T, C, H, W] input - and the encoder runs B + B sequences instead of B + B * T."""
+        B, T = self.B, self.T
+        Lv = self.cfg.video_tokens
+        if "av1" not in self._enc:                                 # ONE single-frame encoder; another frame_index only re-points the patch gather
+            enc = Encoder(self.arena, self.cfg, B, B, self.blocks, self.final, self.dev)
+            enc.norm = _z((2 * B,), F32, self.dev)
+            enc.frame_index = None
+            self._enc["av1"] = enc
+        enc = self._enc["av1"]
+        if enc.frame_index != frame_index:
+            enc.emb_v.set_rows((torch.arange(B) * T + frame_index).repeat_interleave(Lv).to(I32), torch.arange(Lv).repeat(B).to(I32))
+            enc.frame_index = frame_index
+        enc.forward(audio, frames)
+        pooled = enc.pool()
+        ops.l2norm_fwd(pooled[:B], out_a, enc.norm[:B])
+        ops.l2norm_fwd(pooled[B:2 * B], out_v, enc.norm[B:])
+        return out_a, out_v
+
     def _joint_stack(self, nf):
         """Fusion stage for `nf` frames per clip: B*nf sequences [audio tokens | tokens of frame t] (:944,1022)."""
         if nf not in self._joint:

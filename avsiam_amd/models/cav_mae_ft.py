@@ -395,6 +395,35 @@ class CAVMAEFT_BASE(nn.Module):
             return res.clone()
         return tuple(r.clone() for r in res)
 
+    @torch.no_grad()
+    def retrieval_features(self, a, v, frame_index=5, out_a=None, out_v=None):
+        """Clip-level retrieval features: what the retrieval experiment makes of ``forward(a, v, "retrieval")`` (src/retrieval.py:70-78: mean
+        over the tokens, L2 normalisation) -> (audio [B, D], video [B, D]) fp32 unit vectors.  Only frame `frame_index` of every clip goes
+        through the encoder (frames are independent sequences, cav_mae_base.py:901-920), so any T > frame_index is accepted and a ten-frame
+        clip costs 512 + 196 encoder rows instead of 512 + 1960.  out_a / out_v: fp32 [B, D] contiguous device tensors to write into
+        (row slices of a dataset-level feature buffer); None: new tensors."""
+        if not self.arena.p.is_cuda:
+            raise _lib.AvsiamHipError("CAVMAEFT_BASE.retrieval_features needs a GPU: the path runs only on libavsiam_hip.so "
+                                      "(no CPU/eager fallback). Move the model with .cuda() first.")
+        _lib.load()
+        frame_index = int(frame_index)
+        a, v, B, T = self._prepare(a, v, "retrieval")
+        if not 0 <= frame_index < T:
+            raise IndexError(f"retrieval returns frame {frame_index} of each clip (cav_mae_base.py:892); got {T} frames")
+        dev, D = self.arena.p.device, self.cfg.embed_dim
+        outs = []
+        for name, t in (("out_a", out_a), ("out_v", out_v)):
+            if t is None:
+                t = torch.empty((B, D), dtype=torch.float32, device=dev)
+            elif t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (B, D) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous fp32 [{B}, {D}] tensor on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            outs.append(t)
+        eng = self._engine(B, T)
+        if self._shadow_dirty or self.arena.with_grads:
+            self._sync_shadows()
+        eng.retrieval_feats(a, v, outs[0], outs[1], frame_index)
+        return outs[0], outs[1]
+
 
 CAVMAEFT = CAVMAEFT_BASE      # (/root/reference/src/models/__init__.py:8 exports the name; same signature family)
 

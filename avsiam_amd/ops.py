@@ -929,3 +929,84 @@ def adam(p, g, m, v, p_bf16, n, lr, step, beta1=0.95, beta2=0.999, eps=1e-8, wei
         return
     _call("avs_adam", p, g, m, v, p_bf16, n, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
               float(grad_scale), _stream())
+
+
+# ---- retrieval evaluation -------------------------------------------------------------------------------------------------------------
+RETRIEVAL_MAX_TOPK = 16
+_retr_ws = {}            # (device, stream) -> cached workspace: calls on different streams never share one; grown when a call needs more, so no
+                         # allocation per call after the first of a shape.  retrieval_rank_release() drops them
+
+
+def _chk_rows(t, name):
+    """fp32 [n, D] on the GPU whose rows are dense (a row range or row-strided view of a feature buffer is fine)"""
+    if not t.is_cuda:
+        raise _lib.AvsiamHipError(f"{name}: tensor must live on the GPU")
+    if t.dtype != F32:
+        raise _lib.AvsiamHipError(f"{name}: expected {F32}, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise _lib.AvsiamHipError(f"{name}: expected a non-empty [n, D] matrix, got {tuple(t.shape)}")
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise _lib.AvsiamHipError(f"{name}: rows must be dense (strides {t.stride()})")
+
+
+def retrieval_rank_ws_bytes(nq, ng, topk=0):
+    return int(_lib.load().avs_retrieval_rank_ws_bytes(int(nq), int(ng), int(topk)))
+
+
+def retrieval_rank_release():
+    """free the cached workspaces (16 MiB after a 65 536-clip call with topk = 16)"""
+    _retr_ws.clear()
+
+
+def retrieval_rank(q, g, target=None, topk=0, want_sim=False, ws=None):
+    """Rank every query's true match in the gallery without materialising the similarity matrix (src/retrieval.py:32-52).
+
+    q [nq, D], g [ng, D] fp32 (normalised or not); s = q @ g.T in exact fp32, one k-ascending chain per element.  target: int32 [nq] gallery
+    index of each query's match (None: query i matches gallery entry i; needs nq <= ng; values must lie in 0..ng-1 - a value outside is
+    not read and gives target_sim NaN, rank 0).  Returns a dict of device tensors:
+      rank [nq] int32        number of OTHER gallery entries strictly more similar than the match (0 = retrieved first)
+      ties [nq] int32        number of other entries exactly as similar as the match.  The reference's compute_metrics emits one entry per tied
+                             column (so its len(ind) exceeds N); here the optimistic rank and the tie count are reported instead
+      target_sim [nq] fp32   s[i, target[i]], the very bits the comparison used
+      topk_idx / topk_sim    [nq, topk] (topk in 1..16): best entries by (similarity descending, index ascending); -1 / -inf beyond ng
+      sim [nq, ng]           only with want_sim
+    ws: a uint8 device tensor of at least retrieval_rank_ws_bytes(nq, ng, topk) bytes from the caller's pool; None: a cached one.
+    Deterministic: two calls return identical bytes."""
+    _chk_rows(q, "retrieval.q"); _chk_rows(g, "retrieval.g")
+    nq, D = q.shape
+    ng = g.shape[0]
+    if g.shape[1] != D or g.device != q.device:
+        raise _lib.AvsiamHipError(f"retrieval: q {tuple(q.shape)} on {q.device} and g {tuple(g.shape)} on {g.device} do not match")
+    topk = int(topk)
+    if not 0 <= topk <= RETRIEVAL_MAX_TOPK:
+        raise _lib.AvsiamHipError(f"retrieval: topk = {topk} outside 0..{RETRIEVAL_MAX_TOPK}")
+    if target is None:
+        if nq > ng:
+            raise _lib.AvsiamHipError(f"retrieval: target=None pairs query i with gallery entry i, but nq = {nq} > ng = {ng}")
+    else:
+        _chk(target, I32, "retrieval.target", 1)
+        if target.numel() != nq or target.device != q.device:
+            raise _lib.AvsiamHipError(f"retrieval.target: expected {nq} indices on {q.device}, got {tuple(target.shape)} on {target.device}")
+    dev = q.device
+    need = retrieval_rank_ws_bytes(nq, ng, topk)
+    if ws is None:
+        key = (dev, _stream())
+        ws = _retr_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _retr_ws[key] = torch.empty(need, dtype=U8, device=dev)
+    else:
+        _chk(ws, U8, "retrieval.ws")
+        if ws.numel() < need or ws.device != dev:
+            raise _lib.AvsiamHipError(f"retrieval.ws: {ws.numel()} bytes on {ws.device}, need {need} on {dev}")
+    out = {"rank": torch.empty(nq, dtype=I32, device=dev), "ties": torch.empty(nq, dtype=I32, device=dev),
+           "target_sim": torch.empty(nq, dtype=F32, device=dev)}
+    if topk:
+        out["topk_idx"] = torch.empty((nq, topk), dtype=I32, device=dev)
+        out["topk_sim"] = torch.empty((nq, topk), dtype=F32, device=dev)
+    if want_sim:
+        out["sim"] = torch.empty((nq, ng), dtype=F32, device=dev)
+    ldq = q.stride(0) if nq > 1 else D
+    ldg = g.stride(0) if ng > 1 else D
+    _launch("retrieval_rank", 2.0 * nq * ng * D, "avs_retrieval_rank", q, ldq, nq, g, ldg, ng, D, target, out["rank"], out["ties"], out["target_sim"],
+            topk, out.get("topk_idx"), out.get("topk_sim"), out.get("sim"), ng if want_sim else 0, ws, ws.numel(), _stream())
+    return out

@@ -15,6 +15,7 @@
  */
 #ifndef AVSIAM_HIP_H
 #define AVSIAM_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -44,6 +45,8 @@ int avs_device_cu_count(void);
  *               atomics-free positional scatter and un-shuffle token sums: two runs of a step give the same bits (a debugging mode, slower;
  *               the reference gets the same from torch.use_deterministic_algorithms).  The host also keeps the step on ONE stream and takes the
  *               fc1 bias gradient by avs_colsum_bf16 instead of the GEMM epilogue's atomics (EngineOptions.deterministic)
+ *   "retr_segments" 0 (default) automatic | 1..64: gallery-column segments per query panel of avs_retrieval_rank (every value gives the same
+ *               bytes; avs_retrieval_rank_ws_bytes follows the knob, so size the workspace after setting it)
  * avs_persistent_cu_slots(): the CUs a persistent grid fills now (device CUs - cu_reserve). */
 int avs_tuning_set(const char* name, int value);
 int avs_tuning_get(const char* name, int* value);
@@ -376,6 +379,27 @@ int avs_gemm_f32_small(const float* A, long long sam, long long sak, const float
 int avs_infonce_fwd(const float* total, float* stats, float* out, int N, float weight, avs_stream_t stream);
 int avs_infonce_dlogits(const float* total, const float* stats, const float* gout, float weight, float* dtotal, int N,
                         avs_stream_t stream);
+
+/* ---- retrieval evaluation: similarity -> rank of the true match, ties, top-K, in one streaming pass (get_sim_mat + compute_metrics,
+ * src/retrieval.py:32-52; there a Python double loop of numpy.dot over an N x N matrix that is then sorted row by row).
+ * q [nq, D] / ldq, g [ng, D] / ldg fp32 (L2-normalised or not: the kernel does not care).  s[i][j] = sum_k q[i][k] g[j][k] in fp32 on the
+ * f32-input matrix cores, ONE accumulator chain per element with k ascending and no split-K: (i, j) has one value however the grid is cut.
+ *   target [nq] (may be NULL = identity, needs nq <= ng): gallery index of each query's true match.  A value outside 0..ng-1 is not read:
+ *       that row gets target_sim = NaN, rank = ties = 0
+ *   rank[i]  = #{ j != target[i] : s[i][j] >  s[i][target[i]] }   (j == target[i] is excluded by index, never by comparing values)
+ *   ties[i]  = #{ j != target[i] : s[i][j] == s[i][target[i]] }   (may be NULL)
+ *   target_sim[i] = s[i][target[i]], bitwise the value the tile loop sees for that element (may be NULL)
+ *       On tie-free input rank is exactly compute_metrics' `ind`; with ties the reference emits one entry per tied column (len(ind) > N) -
+ *       here the optimistic rank and the tie count are reported instead
+ *   topk in 0..16: topk_idx / topk_sim [nq, topk] = the best gallery entries of row i ordered by (similarity descending, index ascending);
+ *       slots beyond ng hold index -1 / -inf.  Both NULL when topk == 0
+ *   sim / ldsim: optional full [nq, ng] output (NULL: the matrix is never materialised)
+ *   ws: avs_retrieval_rank_ws_bytes(nq, ng, topk) bytes, O(nq * segments * topk), never O(nq * ng).  Counts are integer atomics and the
+ *       top-K order is total: two calls give identical bytes.  Argument errors return -2 before any launch. */
+int avs_retrieval_rank(const float* q, long long ldq, int nq, const float* g, long long ldg, int ng, int D, const int* target, int* rank,
+                       int* ties, float* target_sim, int topk, int* topk_idx, float* topk_sim, float* sim, long long ldsim, void* ws,
+                       size_t ws_bytes, avs_stream_t stream);
+size_t avs_retrieval_rank_ws_bytes(int nq, int ng, int topk);
 
 /* ---- classification loss of the fine-tuning loop (src/traintest_ft_base.py:105-110 loss_fn, :156-160 applied to out / out_a / out_v, the
  * backward of :171).  logits x [n, L] (row stride ldx: the head's output buffer is padded), targets y [n, L] (ldy).

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / LDS / occupancy table of one source's kernels with the product's flags:  bash tools/kernel_regs.sh attention.hip [filter-regex] [extra hipcc flags...]
-SRC=${1:-attention.hip}; FILT=${2:-.}; shift 2 2>/dev/null
+SRC=${1:-attention.hip}; FILT=${2:-.}; [ $# -gt 0 ] && shift; [ $# -gt 0 ] && shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 EXTRA=""; [ "$SRC" = attention.hip ] && EXTRA="-fno-slp-vectorize"
 T=$(mktemp -d)
