@@ -115,7 +115,7 @@ class EngineOptions:
     `CAVMAE_BASE.set_options`, which drops the engines.  RUNTIME fields are read on every call.
 
     fp8           "0" bf16 operands (the headline metric) | "1" e4m3 forward GEMMs | "2" + e5m2 x e4m3 input gradients | "3" + fp8 weight
-                  gradients (BASELINE.json configs[4]'s "fp8 MFMA path"; engine.Stack)                                           [structural]
+                  gradients (BASELINE.json configs[4]'s "fp8 MFMA path"; engine_fp8.Fp8Stack)                                   [structural]
     fp8_lean      mode 3: producers whose bf16 output has no reader left write the 8-bit copy only                                [structural]
     fp8_gelu8     modes 2 / 3: gelu'(x) travels between the fc1 forward and fc2 input-gradient epilogues as 8-bit codes           [structural]
     gelu8         the same 8-bit gelu'(x) codes in the BF16 path (round 6, default ON: every golden / oracle assertion holds at unchanged

@@ -19,6 +19,8 @@ The mask plan (which tokens each sample keeps) is an explicit input - see maskpl
 import math
 import os
 
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -31,50 +33,12 @@ BF16, F32, I32, U8 = torch.bfloat16, torch.float32, torch.int32, torch.uint8
 LN_EPS_BLOCK, LN_EPS_FINAL = 1e-5, 1e-6       # nn.LayerNorm default in Block; timm ViT final norm
 
 
-# Per-layer activation recompute (AVSIAM_RECOMPUTE=1 / bench.py --recompute): a Stack keeps only the fp32 input of every block and
-# re-runs the block's forward (without its last GEMM) in front of the block's backward.  For shapes whose saved activations do not fit
-# 288 GB (ViT-H at batch 64 x 10 frames); costs about 8/12 of the forward GEMMs plus the attention forward again.
-# A FRACTION (AVSIAM_RECOMPUTE=0.5 / bench.py --recompute 0.5) recomputes only the first ceil(f x nblocks) blocks of every Stack and
-# saves the others' activations as usual: the memory between "everything recomputed" (75 GiB at ViT-H/14, batch 64) and the card's
-# 288 GB buys back the same share of the recompute time.
-# -> EngineOptions.recompute (config.py): a property of the model, seeded by AVSIAM_RECOMPUTE.
-
-
 def recompute_blocks(nblocks, setting):
     """number of leading blocks of a Stack of `nblocks` that are recomputed under EngineOptions.recompute ("0" | "1" | a fraction in (0, 1))"""
     f = float(setting)
     if not 0.0 <= f <= 1.0:
         raise ValueError(f"recompute must be 0, 1 or a fraction between them, not {f}")
     return min(nblocks, int(math.ceil(f * nblocks - 1e-9)))
-# fp8 forward (AVSIAM_FP8=1 / bench.py --fp8; BASELINE configs[4]'s "fp8 MFMA path", never the default): the four forward GEMMs of a
-# block (qkv, proj, fc1, fc2) take OCP e4m3 operands with per-tensor DELAYED scaling and accumulate in fp32.  Every quantised tensor has a
-# device record {scale, 1/scale, running amax, saturation events} (ops.Fp8Records): the kernel that produces an operand (the LayerNorm
-# in front of qkv / fc1, the attention epilogue in front of proj, fc1's GELU epilogue in front of fc2, a quantising pass for the
-# weights) reads the scale from the record and folds the |max| it saw into it; once per forward one tiny kernel turns the amax history
-# (16 steps) into the next scales, 448 / (2 * max) - no host synchronisation anywhere, saturation is counted, the state is saved with
-# the checkpoint (CAVMAE_BASE.fp8_state).  The first time a GEMM runs its operands are calibrated on the spot (absmax -> scale, still
-# on the device) and the activation is quantised by a pass.  The MAE pass's two towers run as one stack with two weight sets here too.
-# Everything the backward reads is still produced in bf16.  AVSIAM_FP8=2 (bench.py --fp8 --fp8-dgrad) extends the mode into the backward:
-# ALL FOUR input-gradient GEMMs of a block - fc2 (with its GELU' epilogue), fc1, proj and (round 4) qkv - run on e5m2 gradient operands,
-# written, beside the bf16 gradient the weight-gradient GEMMs and LayerNorm still read, by the kernels that produce them: the LayerNorm
-# backward (residual gradient), the fc2 input-gradient epilogue and the three attention backward kernels (dqkv; avs_attn_bwd_q8 /
-# avs_attn_bwd_fused_q8); own records, fmax 57344 - against the e4m3 copy of the transposed weight (the forward's weight scale).
-# The weight gradients stay bf16.
-# -> EngineOptions.fp8 ("0" | "1" | "2" | "3"): a property of the model (CAVMAE_BASE(fp8_mode=...), --fp8 at the entry point), seeded by AVSIAM_FP8.
-# AVSIAM_FP8=3 only.  With the weight gradients on fp8 operands four bf16 tensors of a block have no reader left once their consumers'
-# records are calibrated: the two LayerNorm outputs and gelu(x) (read by qkv / fc1 / fc2 and their weight gradients - all in e4m3) and
-# the fc2 input gradient (read by fc1's input- and weight-gradient GEMMs in e5m2; fc1's bias gradient is the fused column sum).  "1"
-# (default): their producers write the 8-bit copy ONLY (NULL bf16 output) and the three activations live in one shared buffer per stack
-# instead of one per block - 2 x D + hidden fewer bf16 values written and kept per token and block, and the GEMM epilogues that wrote
-# them (bound by the write burst of all CUs at once) shrink to 3/5 (fc1) and 1/3 (fc2 input gradient) of their bytes.  "0": A/B.
-# -> EngineOptions.fp8_lean.
-# The residual-GRADIENT stream between the blocks of a stack (AVSIAM_GRAD_STREAM=bf16 | fp32).  bf16 (default): a LayerNorm backward
-# reads the upstream residual gradient from the bf16 copy the previous LayerNorm backward wrote for the GEMMs anyway and writes
-# only its own bf16 copy - 10 instead of 16 bytes per element and call (the kernel is HBM-bound); the sum itself is formed in fp32
-# registers and rounded once per LayerNorm (2 x depth roundings of 2^-9 along a stack: ~0.5 % rms at the bottom of 12 blocks,
-# inside the bf16 operand noise the gradients already carry).  A stack's OUTPUT gradient (block 0) is still written in fp32.
-# fp32: the round-2 behaviour (fp32 stream beside the bf16 copies).
-# -> EngineOptions.grad_stream.
 
 
 def _z(shape, dtype, dev):
@@ -229,7 +193,7 @@ class _LnBatch:
 
 def _ln_bwd(dy, x, mean, rstd, norms, dx, ws, rows, row_mod=None, out_map=None, dres=None, dx_bf16=None, dcol=None, dx8=None, q8=None, batch=None):
     """dcol: bias gradient of the Linear whose output gradient is the dx produced here (column sum fused in-kernel).
-    dx8 / q8: e5m2 copy of dx for an fp8 input-gradient GEMM and its device record.
+    dx8 / q8: 8-bit copy of dx for an input-gradient GEMM on 8-bit operands, and its device record (Stack._ln_bwd_copy).
     batch (_LnBatch): the parameter gradients are reduced by the batch's one launch at the end of the stack's backward, not here."""
     n0 = norms[0]
     n1 = norms[1] if len(norms) > 1 else None
@@ -282,7 +246,7 @@ class _SideStream:
         self.done.clear()
 
 
-# (EngineOptions.wgrad_stream / wgrad_group / fp8_gelu8: runtime and structural options of the model, config.py)
+# (EngineOptions.wgrad_stream / wgrad_group: runtime options of the model, config.py)
 _side_streams = {}
 
 
@@ -307,8 +271,29 @@ class _Inline:
         pass
 
 
+_NO_COPY = {}          # what the 8-bit-copy hooks of Stack add to a kernel call: nothing
+
+
+def fp8_applies(opts, D, hidden):
+    """whether a stack of width D with an MLP of width `hidden` runs on 8-bit GEMM operands: EngineOptions.fp8 asks for it and the fp8 GEMM's
+    tile constraints (N % 256, K % 128) hold; any other stack of the model stays bf16"""
+    return opts.fp8 in ("1", "2", "3") and D % 256 == 0 and hidden % 256 == 0 and D >= 256
+
+
+def make_stack(dev, rows, D, H, hidden, seq_lens, nblocks, row_mod=None, inference=False, pool=None, opts=None, q_rows=0):
+    """The stack every pass builds (arguments: Stack.__init__): an engine_fp8.Fp8Stack where fp8_applies(), else the bf16 Stack."""
+    opts = opts if opts is not None else EngineOptions.from_env()
+    cls = Stack
+    if fp8_applies(opts, D, hidden):
+        from .engine_fp8 import Fp8Stack as cls            # (imported here: engine_fp8 imports this module)
+    return cls(dev, rows, D, H, hidden, seq_lens, nblocks, row_mod, inference=inference, pool=pool, opts=opts, q_rows=q_rows)
+
+
 class Stack:
-    """`nblocks` transformer blocks over a packed [rows, D] fp32 residual stream with saved activations."""
+    """`nblocks` transformer blocks over a packed [rows, D] fp32 residual stream with saved activations, GEMM operands in bf16.
+    Methods marked (hook) are what engine_fp8.Fp8Stack overrides to run the same schedule on 8-bit operands; build stacks with make_stack()."""
+
+    fp8 = fp8_bwd = fp8_wgrad = fp8_lean = False          # (the model and the tests ask every stack; Fp8Stack sets them)
 
     def __init__(self, dev, rows, D, H, hidden, seq_lens, nblocks, row_mod=None, inference=False, pool=None, opts=None, q_rows=0):
         """inference=True: forward only - no activation is kept, every block reuses one set of buffers (the residual stream
@@ -325,7 +310,6 @@ class Stack:
         assert pool is None or not inference
         self.pool = pool
         self.opts = opts = opts if opts is not None else EngineOptions.from_env()
-        FP8, FP8_LEAN, FP8_GELU8 = opts.fp8, opts.fp8_lean, opts.fp8_gelu8
         self._pads = ops.ZeroTable() if pool is not None else None
 
         def _z(shape, dtype, dev_):          # (shadows the module's _z for every allocation below)
@@ -341,48 +325,56 @@ class Stack:
         self.inference = inference
         self.nrecomp = 0 if inference else recompute_blocks(nblocks, opts.recompute)     # blocks [0, nrecomp) keep no activations (one shared set)
         self.recompute = self.nrecomp > 0
-        self.fp8 = FP8 in ("1", "2", "3") and D % 256 == 0 and hidden % 256 == 0 and D >= 256     # the fp8 GEMM's tile constraints (N % 256, K % 128)
-        self.fp8_bwd = self.fp8 and FP8 in ("2", "3") and not inference
-        # FP8 = 3 (round 4): the four weight gradients of a block on fp8 operands too (ops.gemm_tn_fp8_group: e5m2 gradient copies x
-        # e4m3 activation copies).  The e4m3 copy of an activation is then KEPT per block (one more byte per element beside the bf16
-        # copy the attention / LayerNorm backward still read) instead of living in one buffer per stack.
-        self.fp8_wgrad = self.fp8_bwd and FP8 == "3"
-        self.fp8_lean = self.fp8_wgrad and FP8_LEAN          # (see FP8_LEAN)
-        if self.fp8:
-            r8 = ops.pad_rows(rows, 256)
-            self.a8 = _z((r8, max(D, hidden)), U8, dev)      # calibration step only: an activation quantised by a pass
-            # persistent e4m3 copies of the stack's weights (two sets: the MAE pass's second tower), re-quantised with the step's scales by
-            # ONE batched launch per forward once every GEMM is calibrated (ops.Fp8Batch); per block: qkv | proj | fc1 | fc2
-            per_blk = 4 * D * D + 2 * D * hidden
-            self.w8_flat = torch.zeros((2 * nblocks * per_blk,), dtype=U8, device=dev)
-            self.w8_off = {"qkv": 0, "proj": 3 * D * D, "fc1": 4 * D * D, "fc2": 4 * D * D + D * hidden}
-            self.w8_per_blk = per_blk
-            self.w8_batch = None                                                   # built after the calibration forward
-            def blocks8(cols, shared=None):     # per block when the weight gradients read them (recomputed blocks share one, like their bf16 copies)
-                if not self.fp8_wgrad:
-                    one = shared if shared is not None else _z((r8, cols), U8, dev)
-                    return [one] * nblocks
-                one = _z((r8, cols), U8, dev) if self.nrecomp else None
-                return [one if i < self.nrecomp else _z((r8, cols), U8, dev) for i in range(nblocks)]
-            self.ln1_8 = blocks8(D)                                                # e4m3 copy a LayerNorm writes for qkv ...
-            self.ln2_8 = blocks8(D, None if self.fp8_wgrad else self.ln1_8[0])     # ... and for fc1 (one buffer serves both unless they are kept)
-            self.att8 = blocks8(D)                                                 # ... the attention epilogue for proj
-            self.act8 = blocks8(hidden)                                            # ... and fc1's GELU epilogue for fc2
-            self.f8 = ops.Fp8Records(nblocks * 12, dev)                            # per block: 4 GEMMs x (activation, weight, second weight set)
-            self.f8_seen = set()                                                   # (block, gemm) whose records hold a calibrated scale
-        if self.fp8_bwd:
-            self.g8 = ops.Fp8Records(nblocks * 4, dev, fmax=ops.BF8_MAX)           # per block: the e5m2 operands dbo (fc2), dfc1 (fc1), dbm (proj)
-            self.g8_seen, self.g8_have = set(), set()
-            self.dx8 = [_z((r8, D), U8, dev) for _ in range(2)]      # e5m2 copies of dbo / dbm
-            self.dfc1_8 = _z((r8, hidden), U8, dev)
-            self.dqkv8 = _z((r8, 3 * D), U8, dev)           # e5m2 copy of dqkv, written by the attention backward kernels
-            per_blk_t = 4 * D * D + 2 * D * hidden                                # transposed copies the fp8 input-gradient GEMMs read: fc2 | fc1 | proj | qkv
-            self.wt8_flat = torch.zeros((2 * nblocks * per_blk_t,), dtype=U8, device=dev)
-            self.wt8_off = {"fc2": 0, "fc1": D * hidden, "proj": 2 * D * hidden, "qkv": 2 * D * hidden + D * D}
-            self.wt8_per_blk = per_blk_t
-            self.wt8_batch = None
+        self._ln_batches, self._vm_batches = {}, {}       # batched reduces of the backward, per (blocks, blocks2, split) it has run with
+        self._alloc_operand_copies(_z, dev)
         rp = ops.pad_rows(rows, 128)
         self.rp = rp
+        self._select_attention(seq_lens, dev)
+        self.q_scale = ops.attn_q_scale(D // H)          # q leaves the qkv GEMM ready for the attention kernels
+
+        def per_block(shape, dtype):
+            if inference:                                     # one buffer for all blocks
+                return [_z(shape, dtype, dev)] * nblocks
+            # recomputed blocks share one buffer, refilled in front of each one's backward; the others keep their own
+            one = _z(shape, dtype, dev) if self.nrecomp else None
+            return [one if i < self.nrecomp else _z(shape, dtype, dev) for i in range(nblocks)]
+
+        if inference:
+            ping = [_z((rp, D), F32, dev) for _ in range(2)]
+            self.x = [ping[i & 1] for i in range(nblocks + 1)]
+        else:
+            self.x = [_z((rp, D), F32, dev) for _ in range(nblocks + 1)]     # x[i] = input of block i; x[-1] = output
+        def one_for_all(shape, dtype):
+            return [_z(shape, dtype, dev)] * nblocks
+        shared, codes = self._buffer_policy()
+        operand = one_for_all if shared else per_block
+        self.xmid = per_block((rp, D), F32)
+        self.ln1 = operand((rp, D), BF16)
+        self.ln2 = self.ln1 if (inference or shared) else per_block((rp, D), BF16)
+        self.qkv = per_block((rp, 3 * D), BF16)
+        self.att = per_block((rp, D), BF16)
+        self.fc1 = per_block((rp, hidden), U8 if codes else BF16)      # gelu'(fc1 output): all the backward needs of the pre-activation (gemm act 1 / 2)
+        self.act = operand((rp, hidden), BF16)
+        self.lse = per_block((H, rp), F32)
+        nshared = nblocks if inference else self.nrecomp
+        st = [_z((rp,), F32, dev) for _ in range(4)] if nshared else None
+        self.stats = [st if i < nshared else [_z((rp,), F32, dev) for _ in range(4)] for i in range(nblocks)]   # mean1 rstd1 mean2 rstd2
+        if inference:
+            return
+        # backward scratch (shared by all blocks)
+        self.dx = [_z((rp, D), F32, dev) for _ in range(2)]
+        self.dxb = [_z((rp, D), BF16, dev) for _ in range(2)]
+        self.dfc1 = _z((rp, hidden), BF16, dev)
+        self.dln = _z((rp, D), BF16, dev)
+        self.datt = _z((rp, D), BF16, dev)
+        self.dqkv = _z((rp, 3 * D), BF16, dev)
+        self.delta = _z((H, rp), F32, dev)
+        self.lnws = _z((ops.layernorm_ws(rows, D),), F32, dev)
+        self._setup_pruned(q_rows, seq_lens, dev)
+
+    def _select_attention(self, seq_lens, dev):
+        """tile tables of the attention kernels: self.tiles (forward), self.fused_bwd / self.tiles_bwd (backward)"""
+        opts, rows, D, H, inference = self.opts, self.rows, self.D, self.H, self.inference
         # rows per attention workgroup (4 or 2 waves of 32 queries / keys), by the mean sequence length of the stack - measured on the
         # step's mixes (tools/bench_attn.py --step): the backward of the contrastive pass (39-196 video, 102-512 audio tokens) is 12 %
         # faster with 64-row workgroups, its forward 11 % slower; 49/128-token towers: forward 10 % faster; 618 and 2472 tokens: 128
@@ -405,8 +397,8 @@ class Stack:
             if cut:
                 self.fused_bwd = [sq for sq in (ops.AttnSeqs(seq_lens, dev, 0, 64), ops.AttnSeqs(seq_lens, dev, 64, cut)) if sq.nseq]
                 # round 6: sequences of 129 .. 224 tokens at head dim 64 (the encoder's 156 / 196-token frames, 204-token audio) in one 7-wave workgroup
-                # per (sequence, head) whose dS image holds the queries in two halves (attn_bwd_fused224_kernel); not with the e5m2 copy of dqkv
-                if D // H == 64 and not self.fp8_bwd and opts.attn_fused224:
+                # per (sequence, head) whose dS image holds the queries in two halves (attn_bwd_fused224_kernel)
+                if D // H == 64 and self._fused224():
                     big = ops.AttnSeqs(seq_lens, dev, 128, 224)
                     if big.nseq:
                         self.fused_bwd.append(big)
@@ -414,52 +406,13 @@ class Stack:
             long_lens = [L for L in seq_lens if L > cut]
             mean_long = sum(long_lens) / max(1, len(long_lens))
             self.tiles_bwd = ops.AttnTiles(seq_lens, dev, tile_rows=force or (64 if mean_long < 256 else 128), min_len=cut)
-        self.q_scale = ops.attn_q_scale(D // H)          # q leaves the qkv GEMM ready for the attention kernels
 
-        def per_block(shape, dtype):
-            if inference:                                     # one buffer for all blocks
-                return [_z(shape, dtype, dev)] * nblocks
-            # recomputed blocks share one buffer, refilled in front of each one's backward; the others keep their own
-            one = _z(shape, dtype, dev) if self.nrecomp else None
-            return [one if i < self.nrecomp else _z(shape, dtype, dev) for i in range(nblocks)]
-
-        if inference:
-            ping = [_z((rp, D), F32, dev) for _ in range(2)]
-            self.x = [ping[i & 1] for i in range(nblocks + 1)]
-        else:
-            self.x = [_z((rp, D), F32, dev) for _ in range(nblocks + 1)]     # x[i] = input of block i; x[-1] = output
-        def one_for_all(shape, dtype):                        # fp8 mode 3: a bf16 tensor only the calibration step still writes
-            return [_z(shape, dtype, dev)] * nblocks
-        lean = getattr(self, "fp8_lean", False)
-        self.xmid = per_block((rp, D), F32)
-        self.ln1 = (one_for_all if lean else per_block)((rp, D), BF16)
-        self.ln2 = self.ln1 if (inference or lean) else per_block((rp, D), BF16)
-        self.qkv = per_block((rp, 3 * D), BF16)
-        self.att = per_block((rp, D), BF16)
-        # gelu'(fc1 output): all the backward needs of the pre-activation (gemm act 1 / 2).  With the fp8 backward (modes 2 / 3) it travels as 8-bit
-        # fixed-point codes (ops.gemm_nt_fp8: a uint8 `out` / `aux`): half the bytes of the two epilogues that write and read it (AVSIAM_FP8_GELU8=0: A/B)
-        # EngineOptions.gelu8 (default on since round 6): the same codes in the bf16 path
-        self.fc1 = per_block((rp, hidden), U8 if ((getattr(self, "fp8_bwd", False) and FP8_GELU8) or (opts.gelu8 and not self.fp8 and not inference)) else BF16)
-        self.act = (one_for_all if lean else per_block)((rp, hidden), BF16)
-        self.lse = per_block((H, rp), F32)
-        nshared = nblocks if inference else self.nrecomp
-        st = [_z((rp,), F32, dev) for _ in range(4)] if nshared else None
-        self.stats = [st if i < nshared else [_z((rp,), F32, dev) for _ in range(4)] for i in range(nblocks)]   # mean1 rstd1 mean2 rstd2
-        if inference:
-            return
-        # backward scratch (shared by all blocks)
-        self.dx = [_z((rp, D), F32, dev) for _ in range(2)]
-        self.dxb = [_z((rp, D), BF16, dev) for _ in range(2)]
-        self.dfc1 = _z((rp, hidden), BF16, dev)
-        self.dln = _z((rp, D), BF16, dev)
-        self.datt = _z((rp, D), BF16, dev)
-        self.dqkv = _z((rp, 3 * D), BF16, dev)
-        self.delta = _z((H, rp), F32, dev)
-        self.lnws = _z((ops.layernorm_ws(rows, D),), F32, dev)
-        # ---- pruned last block (q_rows): applies to bf16 stacks of equal-length sequences with plain norms, the bf16 gradient stream and the
+    def _setup_pruned(self, q_rows, seq_lens, dev):
+        """the pruned last block (Stack.__init__, q_rows): sets self.lq and the row maps where the form applies"""
+        opts, rows, nblocks, row_mod = self.opts, self.rows, self.nblocks, self.row_mod
+        # applies to stacks of equal-length sequences with plain norms, the bf16 gradient stream and the
         # two-kernel attention backward (the decoder: 2 472-token sequences)
-        self.lq = 0
-        if (q_rows and not self.fp8 and row_mod is None and opts.grad_stream == "bf16" and self.tiles.uniform_len and self.tiles_bwd.uniform_len
+        if (q_rows and row_mod is None and opts.grad_stream == "bf16" and self.tiles.uniform_len and self.tiles_bwd.uniform_len
                 and not self.fused_bwd and 0 < q_rows < seq_lens[0] and nblocks >= 1):
             L, nseq = seq_lens[0], len(seq_lens)
             self.lq, self.Mq = int(q_rows), nseq * int(q_rows)
@@ -477,6 +430,19 @@ class Stack:
                     self._qpads.add(buf[self.Mq:padq])
                 self._qpads.build(dev)
 
+    # ---- hooks of the constructor
+    def _alloc_operand_copies(self, z, dev):
+        """(hook) buffers allocated ahead of the activations (z: the constructor's allocator): none here"""
+
+    def _fused224(self):
+        """(hook) whether the 7-wave fused attention backward (129 .. 224 tokens) may be selected"""
+        return self.opts.attn_fused224
+
+    def _buffer_policy(self):
+        """(hook) (shared, codes).  shared: the GEMM operands ln1 / ln2 / act live in one buffer for all blocks instead of one per block;
+        codes: gelu'(x) travels from fc1 to the fc2 input-gradient GEMM as 8-bit fixed-point codes instead of bf16 (EngineOptions.gelu8)"""
+        return False, bool(self.opts.gelu8 and not self.inference)
+
     @property
     def out(self):
         return self.x[self.nblocks]
@@ -489,49 +455,20 @@ class Stack:
             if self._pads.desc is None and self._pads.entries:
                 self._pads.build(self.x[0].device)
             self._pads.run()
-        if self.fp8:
-            self.f8.update()                   # delayed scaling: last forward's amax -> history -> this forward's scales (one launch)
-            nsets = 2 if blocks2 is not None else 1
-            if self.w8_batch is None and len(self.f8_seen) == 4 * self.nblocks:      # every GEMM calibrated: freeze the weight table
-                self.w8_batch = ops.Fp8Batch(self.f8)
-                for i, bp in enumerate(blocks):
-                    for name in ("qkv", "proj", "fc1", "fc2"):
-                        for st_, bl in enumerate((bp, blocks2[i] if blocks2 is not None else None)[:nsets]):
-                            self.w8_batch.add(getattr(bl, name).w, self._w8(i, name, st_), (i * 4 + self._G8[name]) * 3 + 1 + st_)
-                self.w8_batch.build(self.x[0].device)
-            if self.w8_batch is not None:
-                self.w8_batch.run()            # all weights of the stack -> e4m3 with this step's scales (one launch)
+        self._forward_begin(blocks, blocks2)
         for i, bp in enumerate(blocks):
             self._block_forward(i, bp, blocks2[i] if blocks2 is not None else None, split)
 
-    _G8 = {"qkv": 0, "proj": 1, "fc1": 2, "fc2": 3}
-
-    def _rec(self, i, name, operand=0):
-        return self.f8.rec((i * 4 + self._G8[name]) * 3 + operand)
-
-    def _w8(self, i, name, which=0):
-        """persistent e4m3 copy [N, K] of block i's weight `name` (which: weight set 0 / 1)"""
-        D, Hd = self.D, self.hidden
-        N, K = {"qkv": (3 * D, D), "proj": (D, D), "fc1": (Hd, D), "fc2": (D, Hd)}[name]
-        o = (which * self.nblocks + i) * self.w8_per_blk + self.w8_off[name]
-        return self.w8_flat[o:o + N * K].view(N, K)
-
-    def _wt8(self, i, name, which=0):
-        """persistent e4m3 copy of the TRANSPOSED weight (B operand [K_in, N_out] of the input-gradient GEMM)"""
-        D, Hd = self.D, self.hidden
-        N, K = {"fc2": (Hd, D), "fc1": (D, Hd), "proj": (D, D), "qkv": (D, 3 * D)}[name]
-        o = (which * self.nblocks + i) * self.wt8_per_blk + self.wt8_off[name]
-        return self.wt8_flat[o:o + N * K].view(N, K)
+    def _forward_begin(self, blocks, blocks2):
+        """(hook) in front of the first block of a forward: nothing here"""
 
     def _block_forward(self, i, bp, b2, split, last_gemm=True):
-        """Block i: x[i] -> x[i + 1] and everything its backward reads.  last_gemm=False (recompute in front of the backward): x[i + 1]
+        """(hook) Block i: x[i] -> x[i + 1] and everything its backward reads.  last_gemm=False (recompute in front of the backward): x[i + 1]
         is not needed again, the fc2 GEMM is skipped."""
         M = self.rows
         x, st = self.x[i], self.stats[i]
         n1 = bp.n1 if b2 is None else [bp.n1[0], b2.n1[0]]
         n2 = bp.n2 if b2 is None else [bp.n2[0], b2.n2[0]]
-        if self.fp8:
-            return self._block_forward_fp8(i, bp, b2, split, last_gemm, n1, n2)
         if self.lq and i == self.nblocks - 1:
             # pruned last block (see __init__): every row is a key / value, the first lq rows of a sequence are the queries; from the attention
             # output on the block lives on the compact rows
@@ -560,103 +497,7 @@ class Stack:
         if last_gemm:
             ops.gemm_nt(self.act[i], bp.fc2.w, self.x[i + 1], M, bias=bp.fc2.b, res=self.xmid[i], dual=d2)
 
-    def _block_forward_fp8(self, i, bp, b2, split, last_gemm, n1, n2):
-        """The block's forward with e4m3 GEMM operands (module comment at FP8).  Once a GEMM's records are calibrated its activation
-        arrives in e4m3 from the kernel that produces it; before that (first use) it is quantised by a pass."""
-        M = self.rows
-        x, st = self.x[i], self.stats[i]
-        seen = lambda name: (i, name) in self.f8_seen
-        r = lambda name: self._rec(i, name)
-        l1, l2, at8, ac8 = self.ln1_8[i], self.ln2_8[i], self.att8[i], self.act8[i]
-        lean = self.fp8_lean               # a calibrated consumer reads the e4m3 copy only, and so does its weight gradient: no bf16 output
-        _ln_fwd(x, n1, None if lean and seen("qkv") else self.ln1[i], st[0], st[1], M, LN_EPS_BLOCK, self.row_mod, y8=l1 if seen("qkv") else None,
-                q8_dev=r("qkv") if seen("qkv") else None)
-        self._gemm_fp8(i, "qkv", self.ln1[i], l1, bp.qkv, b2.qkv if b2 else None, split, self.qkv[i], scale_cols=self.D, col_scale=self.q_scale)
-        ops.attn_fwd(self.qkv[i], self.tiles, self.H, self.att[i], self.lse[i], **({"out8": at8, "q8": r("proj")} if seen("proj") else {}))
-        self._gemm_fp8(i, "proj", self.att[i], at8, bp.proj, b2.proj if b2 else None, split, self.xmid[i], res=x)
-        _ln_fwd(self.xmid[i], n2, None if lean and seen("fc1") else self.ln2[i], st[2], st[3], M, LN_EPS_BLOCK, self.row_mod, y8=l2 if seen("fc1") else None,
-                q8_dev=r("fc1") if seen("fc1") else None)
-        # (the fc2 weight gradient reads the e4m3 copy of gelu(x) too: with fp8 weight gradients it is written even when fc2 itself is skipped)
-        o8 = {"out8": ac8, "q8": r("fc2")} if (seen("fc2") and (last_gemm or self.fp8_wgrad)) else {}
-        self._gemm_fp8(i, "fc1", self.ln2[i], l2, bp.fc1, b2.fc1 if b2 else None, split, self.fc1[i], out2=None if lean and o8 else self.act[i], act=1, **o8)
-        if last_gemm:
-            self._gemm_fp8(i, "fc2", self.act[i], ac8, bp.fc2, b2.fc2 if b2 else None, split, self.x[i + 1], res=self.xmid[i])
-        elif self.fp8_wgrad and not seen("fc2"):
-            raise RuntimeError("fp8 weight gradients: a recomputed block met an uncalibrated fc2 record")
-
-    def _gemm_fp8(self, i, name, A, a8, lin, lin2, split, out, **kw):
-        """One forward GEMM on e4m3 operands.  a8: where this GEMM's activation lives in e4m3 once its producer writes it."""
-        M = self.rows
-        W, W2 = lin.w, (lin2.w if lin2 is not None else None)
-        N, K = W.shape
-        ra, rw, rw2 = self._rec(i, name, 0), self._rec(i, name, 1), self._rec(i, name, 2)
-        first = (i, name) not in self.f8_seen
-        if first:                                  # calibrate on the spot, on the device: amax -> record -> scale (no host sync)
-            ops.absmax_into(A, ra)
-            ops.absmax_into(W, rw)
-            if W2 is not None:
-                ops.absmax_into(W2, rw2)
-            self.f8.update(first=(i * 4 + self._G8[name]) * 3, count=3)
-            self.f8_seen.add((i, name))
-            if self.fp8_wgrad:                     # the block's own e4m3 copy: the weight gradient of this step reads it
-                a8 = a8[:A.shape[0]]
-            else:
-                a8 = self.a8[:A.shape[0], :K] if self.a8.shape[1] == K else self.a8.view(-1)[:A.shape[0] * K].view(A.shape[0], K)
-            ops.quantize_fp8(A, 1.0, out=a8, q=ra)
-        w8 = self._w8(i, name, 0)
-        w8b = self._w8(i, name, 1) if W2 is not None else None
-        if self.w8_batch is None:                  # until the table exists (calibration forward): one quantising pass per weight
-            ops.quantize_fp8(W, 1.0, out=w8, q=rw)
-            if W2 is not None:
-                ops.quantize_fp8(W2, 1.0, out=w8b, q=rw2)
-        dual = (split, w8b, lin2.b, rw2) if W2 is not None else None
-        ops.gemm_nt_fp8(a8, w8, out, M, bias=lin.b, qa=ra, qw=rw, dual=dual, **kw)
-
-    def _dgrad_fp8(self, i, gname, wname, A, a8, lin, lin2, split, out, colsum2=None, **kw):
-        """One input-gradient GEMM on an e5m2 gradient operand (A: its bf16 form, a8: where its e5m2 copy lives - written by the
-        producer when (i, gname) is in g8_have, else by a pass here) and the e4m3 copy of the transposed weight, quantised with the
-        scale of the forward's weight record (the same tensor)."""
-        M = self.rows
-        G8 = {"dbo": 0, "dfc1": 1, "dbm": 2, "dqkv": 3}
-        idx = i * 4 + G8[gname]
-        rec = self.g8.rec(idx)
-        if (i, gname) not in self.g8_seen:            # first use: calibrate on the device
-            ops.absmax_into(A, rec)
-            self.g8.update(first=idx, count=1)
-            self.g8_seen.add((i, gname))
-        if (i, gname) not in self.g8_have:
-            ops.quantize_fp8(A, 1.0, out=a8[:A.shape[0]], q=rec, e5m2=True)
-        rw, rw2 = self._rec(i, wname, 1), self._rec(i, wname, 2)
-        w8 = self._wt8(i, wname, 0)
-        w8b = self._wt8(i, wname, 1) if lin2 is not None else None
-        if self.wt8_batch is None:                 # first backward: per-weight passes, and the table for the batched launch is collected
-            pend = self.__dict__.setdefault("_wt8_pending", [])
-            base = (i * 4 + self._G8[wname]) * 3
-            ops.quantize_fp8(lin.wt, 1.0, out=w8, q=rw)
-            pend.append((lin.wt, w8, base + 1))
-            if lin2 is not None:
-                ops.quantize_fp8(lin2.wt, 1.0, out=w8b, q=rw2)
-                pend.append((lin2.wt, w8b, base + 2))
-        dual = (split, w8b, None, rw2, colsum2) if lin2 is not None else None
-        ops.gemm_nt_fp8(a8, w8, out, M, qa=rec, qw=rw, grad=True, dual=dual, **kw)
-
-    def fp8_state(self):
-        """delayed-scaling state for the checkpoint (None without the fp8 mode)"""
-        if not self.fp8:
-            return None
-        st = {**self.f8.state(), "seen": sorted(self.f8_seen)}
-        if self.fp8_bwd:
-            st["grad"] = {**self.g8.state(), "seen": sorted(self.g8_seen)}
-        return st
-
-    def load_fp8_state(self, st):
-        if self.fp8 and st is not None:
-            self.f8.load(st)
-            self.f8_seen = {tuple(k) for k in st["seen"]}
-            if self.fp8_bwd and "grad" in st:
-                self.g8.load(st["grad"])
-                self.g8_seen = {tuple(k) for k in st["grad"]["seen"]}
-
+    # ---- backward: backward() is the schedule of one call; `c` carries the call's arguments and choices to the per-block methods
     def backward(self, blocks, last_fc2_bias_done=False, blocks2=None, split=0, reducer=None, accumulate=False):
         """In: d(out) in self.dxb[0] (bf16) - and in self.dx[0] (fp32) when GRAD_STREAM is "fp32".  Out: d(x[0]) in self.dx[0] (fp32)
         and self.dxb[0].
@@ -670,13 +511,33 @@ class Stack:
         reduces over rows into a parameter gradient (weight-gradient GEMMs, bias column sums, LayerNorm backward with its
         gamma/beta/bias sums) runs once per row range on row slices of the same buffers."""
         assert not self.inference, "Stack(inference=True) keeps no activations"
-        M = self.rows
-        dxo, dxm = self.dx
-        dbo, dbm = self.dxb
-        ranges = [(0, M, blocks)] if blocks2 is None else [(0, split, blocks), (split, M, blocks2)]
-        # a second backward over a block since its gradients were zeroed must say accumulate=True (the value third of the qkv bias gradient is
-        # a vector-matrix product of the WHOLE accumulated proj bias gradient) - checked HERE, before any kernel is queued, so a refused call
-        # leaves the gradient arena untouched (ADVICE r4)
+        ranges = [(0, self.rows, blocks)] if blocks2 is None else [(0, split, blocks), (split, self.rows, blocks2)]
+        self._claim_epoch(ranges, accumulate)
+        c = SimpleNamespace(blocks=blocks, blocks2=blocks2, split=split, ranges=ranges, reducer=reducer, accumulate=accumulate,
+                            last_fc2_bias_done=last_fc2_bias_done, done=set(), ln_batch=None, vm_batch=None)
+        c.one = blocks2 is not None                  # a row range has ONE affine set; the packed single-tower case selects by row_mod
+        c.side, c.excl, c.grp = self._stream_mode()
+        c.g16 = self.opts.grad_stream == "bf16"      # the residual gradient travels between the LayerNorm backwards in bf16 only
+        c.det = bool(self.opts.deterministic)        # one stream, no epilogue atomics; the library's own reductions follow the "det" knob (the model sets it)
+        # the small per-block reduces in ONE launch each at the end of the stack's backward - unless something wants a block's gradients final as it
+        # completes (the data-parallel reducer), the gradients accumulate over two passes, or the deterministic forms are asked for
+        if reducer is None and not accumulate and not c.det and self.opts.batch_reduce:
+            c.ln_batch, c.vm_batch = self._reduce_batches(c)
+        self._backward_begin(c)
+        for i in reversed(range(self.nblocks)):
+            self._block_backward(c, i)
+        c.side.join()
+        if c.ln_batch is not None:
+            c.ln_batch.finish()        # (before the value thirds: they read the complete proj bias gradients, which are LayerNorm-2 column sums)
+        if c.vm_batch is not None:
+            c.vm_batch.run()
+        for j in reversed(range(self.nblocks)):        # (mode 2 has reported all but block 0 on the way)
+            self._block_done(c, j)
+
+    def _claim_epoch(self, ranges, accumulate):
+        """a second backward over a block since its gradients were zeroed must say accumulate=True (the value third of the qkv bias gradient is
+        a vector-matrix product of the WHOLE accumulated proj bias gradient) - checked before any kernel is queued, so a refused call
+        leaves the gradient arena untouched"""
         for lo_, hi_, bl in ranges:
             for i in range(self.nblocks):
                 ar = bl[i].arena
@@ -686,207 +547,178 @@ class Stack:
         for lo_, hi_, bl in ranges:
             for i in range(self.nblocks):
                 bl[i].arena.gb_epoch[bl[i].prefix] = bl[i].arena.zero_epoch
-        one = blocks2 is not None                # a row range has ONE affine set; the packed single-tower case selects by row_mod
-        # recompute: the blocks share ONE set of activation buffers, refilled in front of every block's backward - weight-gradient GEMMs
-        # still reading them on a second stream would race with the refill, so everything runs on one stream
-        # (a partially recomputed stack - engine.RECOMPUTE a fraction - uses the second stream for the blocks that keep their own buffers and
-        #  joins it in front of the first recomputed block, see the loop)
+
+    def _stream_mode(self):
+        """(side, excl, grp) of one backward (_SideStream).  side: where the weight-gradient GEMMs run; excl (mode 2): beside the attention /
+        LayerNorm backward and the column sums only - every nt GEMM waits for them; grp: a block's fc2 / fc1 / proj weight gradients are
+        issued together (one grouped launch) - mode 1 issues each as early as its operands exist.
+        Recompute: the blocks share ONE set of activation buffers, refilled in front of every block's backward - weight-gradient GEMMs still
+        reading them on a second stream would race with the refill, so everything runs on one stream (a partially recomputed stack uses the
+        second stream for the blocks that keep their own buffers and joins it in front of the first recomputed block, _block_backward)."""
         mode = "0" if (self.nrecomp >= self.nblocks or self.opts.deterministic) else self.opts.wgrad_stream
         if mode == "auto":            # small stacks: the weight gradients also fill the partial rounds of the forward / input-gradient GEMMs (config.EngineOptions)
             mode = "2" if self.rows >= 32768 else "1"
-        side = _side_stream(dxo.device) if mode in ("1", "2") else _Inline()
-        excl = mode == "2"            # 2: wgrads run beside attention / LayerNorm / column sums only - every nt GEMM waits for them
-        grp = excl or mode == "0"     # the block's fc2 / fc1 / proj weight gradients are issued together (one grouped launch); mode 1
-                                      # issues each as early as its operands exist
-        g16 = self.opts.grad_stream == "bf16"   # the residual gradient travels between the LayerNorm backwards in bf16 only
-        det = bool(self.opts.deterministic)     # one stream (above), no epilogue atomics; the library's own reductions follow the "det" knob (the model sets it)
-        # the value thirds of the blocks' qkv bias gradients (a [D] x [D, D] product each, below) in ONE launch at the end of the stack's backward instead
-        # of one ~10-us launch per block inside it - unless something wants a block's gradients final as it completes (the data-parallel reducer), the
-        # gradients accumulate over two passes, or the deterministic forms are asked for
-        vm_batch = ln_batch = None
-        if reducer is None and not accumulate and not det and self.opts.batch_reduce:
-            key = (id(blocks), id(blocks2), split)
-            lcache = self.__dict__.setdefault("_ln_batches", {})
-            if key not in lcache:
-                lcache[key] = (_LnBatch(self.D, dxo.device), blocks, blocks2)
-            ln_batch = lcache[key][0]
-            ln_batch.k = 0
-            cache = self.__dict__.setdefault("_vm_batches", {})
-            if key not in cache:
-                vb = ops.VecmatBatch()
-                for lo_, hi_, bl in ranges:
-                    for i in range(self.nblocks):
-                        vb.add(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * self.D:])
-                vb.build(dxo.device)
-                cache[key] = (vb, blocks, blocks2)                # (the parameter lists are kept alive with their id()s)
-            vm_batch = cache[key][0]
+        side = _side_stream(self.dx[0].device) if mode in ("1", "2") else _Inline()
+        return side, mode == "2", mode in ("2", "0")
 
-        done = set()
+    def _reduce_batches(self, c):
+        """(ln_batch, vm_batch): the parameter-gradient reduces of the LayerNorm backwards (_LnBatch) and the value thirds of the blocks' qkv bias
+        gradients (a [D] x [D, D] product each, _attn_backward) as one launch each instead of one ~10-us launch per block"""
+        key, dev = (id(c.blocks), id(c.blocks2), c.split), self.dx[0].device
+        if key not in self._ln_batches:
+            self._ln_batches[key] = (_LnBatch(self.D, dev), c.blocks, c.blocks2)
+        ln_batch = self._ln_batches[key][0]
+        ln_batch.k = 0
+        if key not in self._vm_batches:
+            vb = ops.VecmatBatch()
+            for lo_, hi_, bl in c.ranges:
+                for i in range(self.nblocks):
+                    vb.add(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * self.D:])
+            vb.build(dev)
+            self._vm_batches[key] = (vb, c.blocks, c.blocks2)                # (the parameter lists are kept alive with their id()s)
+        return ln_batch, self._vm_batches[key][0]
 
-        def block_done(j):
-            """Every kernel writing block j's parameter gradients is queued on the current stream or joined into it."""
-            if j in done:
-                return
-            done.add(j)
-            if reducer is not None:
-                for bl in (blocks, blocks2):
-                    if bl is not None:
-                        for a, b in bl[j].ranges:
-                            reducer.ready(a, b)
+    def _block_done(self, c, j):
+        """Every kernel writing block j's parameter gradients is queued on the current stream or joined into it."""
+        if j in c.done:
+            return
+        c.done.add(j)
+        if c.reducer is not None:
+            for bl in (c.blocks, c.blocks2):
+                if bl is not None:
+                    for a, b in bl[j].ranges:
+                        c.reducer.ready(a, b)
 
-        def wgrads(blk, key, *jobs, rows=None):
-            """rows: the jobs' token rows when they are not the stack's (the pruned last block's compact rows)"""
-            def fn():      # the jobs of one call share their token rows: one grouped launch per row range (ops.gemm_tn_group)
-                for lo, hi, bl in (ranges if rows is None else [(0, rows, blocks)]):
-                    if self.fp8_wgrad:
-                        # fp8 mode 3: the e5m2 copy of the gradient (written by its producer or by the input-gradient GEMM's quantising
-                        # pass just before) x the block's e4m3 copy of the layer input, with the two operands' device records
-                        src = {"fc2": (self.dx8[0], "dbo", self.act8), "fc1": (self.dfc1_8, "dfc1", self.ln2_8), "proj": (self.dx8[1], "dbm", self.att8),
-                               "qkv": (self.dqkv8, "dqkv", self.ln1_8)}
-                        jobs8 = []
-                        for a, b, name in jobs:
-                            g8buf, gname, x8 = src[name]
-                            assert (blk, gname) in self.g8_seen and (blk, name) in self.f8_seen
-                            jobs8.append((g8buf[lo:], x8[blk][lo:], getattr(bl[blk], name).gw, self.g8.rec(blk * 4 + G8[gname]), self._rec(blk, name, 0)))
-                        ops.gemm_tn_fp8_group(jobs8, hi - lo)
-                        continue
-                    trip = [(a[lo:], b[lo:], getattr(bl[blk], name).gw) for a, b, name in jobs]
-                    if self.opts.wgrad_group:
-                        ops.gemm_tn_group(trip, hi - lo)
-                    else:
-                        for A, B, C in trip:
-                            ops.gemm_tn(A, B, C, hi - lo)
-            side.run(key, fn)
+    def _wgrads(self, c, blk, key, *jobs, rows=None):
+        """Weight gradients (gradient, layer input, Linear) of block blk on c.side; the jobs of one call share their token rows.
+        rows: the jobs' token rows when they are not the stack's (the pruned last block's compact rows)"""
+        def fn():
+            for lo, hi, bl in (c.ranges if rows is None else [(0, rows, c.blocks)]):
+                self._wgrad(blk, jobs, bl, lo, hi)
+        c.side.run(key, fn)
 
-        f8b = self.fp8_bwd
-        if f8b:
-            self.g8.update()                   # delayed scaling of the gradient operands: last backward's amax -> this backward's scales
-            self.g8_have = set()               # (block, operand) whose e5m2 copy a producer has written in this backward
-            if self.wt8_batch is None and getattr(self, "_wt8_pending", None) is not None and len(self._wt8_pending) == 4 * self.nblocks * (2 if blocks2 is not None else 1):
-                self.wt8_batch = ops.Fp8Batch(self.f8)      # the transposed copies use the forward's weight records (the same tensors)
-                for src, dst, ridx in self._wt8_pending:
-                    self.wt8_batch.add(src, dst, ridx)
-                self.wt8_batch.build(dxo.device)
-            if self.wt8_batch is not None:
-                self.wt8_batch.run()
-        G8 = {"dbo": 0, "dfc1": 1, "dbm": 2, "dqkv": 3}
+    def _wgrad(self, blk, jobs, bl, lo, hi):
+        """(hook) the jobs over one row range [lo, hi) into the gradients of bl[blk]: one grouped launch (ops.gemm_tn_group)"""
+        trip = [(a[lo:], b[lo:], getattr(bl[blk], name).gw) for a, b, name in jobs]
+        if self.opts.wgrad_group:
+            ops.gemm_tn_group(trip, hi - lo)
+        else:
+            for A, B, C in trip:
+                ops.gemm_tn(A, B, C, hi - lo)
 
-        def g8rec(blk, name):                  # (e5m2 buffer, record) of a gradient operand once calibrated, else (None, None)
-            if not f8b or blk < 0 or (blk, name) not in self.g8_seen:
-                return None, None
-            self.g8_have.add((blk, name))
-            return {"dbo": self.dx8[0], "dbm": self.dx8[1], "dfc1": self.dfc1_8, "dqkv": self.dqkv8}[name], self.g8.rec(blk * 4 + G8[name])
+    def _backward_begin(self, c):
+        """(hook) in front of the last block's backward: nothing here"""
 
-        for i in reversed(range(self.nblocks)):
-            bp, st = blocks[i], self.stats[i]
-            b2 = blocks2[i] if blocks2 is not None else None
-            pruned = bool(self.lq) and i == self.nblocks - 1        # the block's upper half (proj ... fc2) lives on the compact rows [0, Mq)
-            Mu = self.Mq if pruned else M
-            assert not pruned or (blocks2 is None and g16 and not f8b)
-            if i < self.nrecomp:
-                if not isinstance(side, _Inline):      # from here down the blocks share one set of activation buffers: one stream
-                    side.join()
-                    if excl and i + 1 < self.nblocks:
-                        block_done(i + 1)
-                    side, excl, grp = _Inline(), False, True
-                self._block_forward(i, bp, b2, split, last_gemm=False)
-            # fc2: d(gelu out) fused with GELU' -> d(fc1 pre-activation)
-            if excl:
-                side.join()
-                if i + 1 < self.nblocks:
-                    block_done(i + 1)          # its last wgrad (qkv) was the side stream's tail; fc2's bias came from this LN backward
-            else:
-                side.before_write("dfc1")
-            if f8b:
-                o8, r8_ = g8rec(i, "dfc1")
-                # (lean mode 3: once the e5m2 copy is written by this epilogue nothing reads the bf16 gradient - no bf16 output)
-                # (deterministic mode: the bf16 gradient is written even in the lean form - the column-sum kernel below reads it)
-                self._dgrad_fp8(i, "dbo", "fc2", dbo, self.dx8[0], bp.fc2, b2.fc2 if b2 else None, split, None if (self.fp8_lean and o8 is not None and not det) else self.dfc1, act=2, aux=self.fc1[i],
-                                colsum=None if det else bp.fc1.gb, colsum2=None if det else (b2.fc1.gb if b2 else None), **({"out8": o8, "q8": r8_} if o8 is not None else {}))
-            else:
-                ops.gemm_nt(dbo, bp.fc2.wt, self.dfc1, Mu, aux=self.fc1[i], act=2, colsum=None if det else bp.fc1.gb,   # + fc1 bias gradient
-                            dual=(split, b2.fc2.wt, None, None if det else b2.fc1.gb) if b2 is not None else None)
-            if det:                   # deterministic mode: the fc1 bias gradient by the column-sum kernel (one writer per element) instead of the epilogue's atomics
-                for lo, hi, bl in (ranges if not pruned else [(0, Mu, blocks)]):
-                    ops.colsum(self.dfc1[lo:], bl[i].fc1.gb, hi - lo)
-            if not grp:
-                wgrads(i, "dbo", (dbo, self.act[i], "fc2"), rows=Mu if pruned else None)
-            if i == self.nblocks - 1 and not last_fc2_bias_done:
-                for lo, hi, bl in (ranges if not pruned else [(0, Mu, blocks)]):
-                    ops.colsum(dbo[lo:], bl[i].fc2.gb, hi - lo)
-            # fc1
-            if f8b:
-                self._dgrad_fp8(i, "dfc1", "fc1", self.dfc1, self.dfc1_8, bp.fc1, b2.fc1 if b2 else None, split, self.dln)
-            else:
-                ops.gemm_nt(self.dfc1, bp.fc1.wt, self.dln, Mu, dual=(split, b2.fc1.wt, None, None) if b2 is not None else None)
-            if not grp:
-                wgrads(i, "dfc1", (self.dfc1, self.ln2[i], "fc1"), rows=Mu if pruned else None)
-                side.before_write("dbm")
-            for lo, hi, bl in (ranges if not pruned else [(0, Mu, blocks)]):
-                if accumulate:            # value third of the qkv bias gradient, below: minus what proj.gb holds before this block adds to it
-                    ops.vecmat(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * self.D:], -1.0)
-                d8, q8_ = g8rec(i, "dbm")
-                _ln_bwd(self.dln[lo:], self.xmid[i][lo:], st[2][lo:], st[3][lo:], bl[i].n2, None if g16 else dxm[lo:], self.lnws, hi - lo,
-                        None if one else self.row_mod, dres=(dbo if g16 else dxo)[lo:], dx_bf16=dbm[lo:], dcol=bl[i].proj.gb,
-                        dx8=d8[lo:] if d8 is not None else None, q8=q8_, batch=ln_batch)
-            # proj
-            if f8b:
-                self._dgrad_fp8(i, "dbm", "proj", dbm, self.dx8[1], bp.proj, b2.proj if b2 else None, split, self.datt)
-            else:
-                ops.gemm_nt(dbm, bp.proj.wt, self.datt, Mu, dual=(split, b2.proj.wt, None, None) if b2 is not None else None)
-            if grp:                   # the three wgrads whose operands exist now run beside the attention backward
-                wgrads(i, "blockA", (dbo, self.act[i], "fc2"), (self.dfc1, self.ln2[i], "fc1"), (dbm, self.att[i], "proj"), rows=Mu if pruned else None)
-            else:
-                wgrads(i, "dbm", (dbm, self.att[i], "proj"), rows=Mu if pruned else None)
-                side.before_write("dqkv")
-            a8 = {}
-            if f8b:                                # the attention backward kernels write the e5m2 copy of dqkv themselves once its record is calibrated
-                d8, q8_ = g8rec(i, "dqkv")
-                if d8 is not None:
-                    # (lean mode 3: the qkv input- and weight-gradient GEMMs read the e5m2 copy; of the bf16 dqkv only the query third has a reader)
-                    a8 = {"dqkv8": d8, "q8": q8_, "kv_bf16": not self.fp8_lean}
-            if pruned:
-                # queries: the first lq rows of every sequence (out / dO compact); dk, dv for every row.  The query third of the other rows of dqkv
-                # is zero by definition (they asked nothing), and the residual gradient of the compact rows goes back into the packed numbering
-                # for LayerNorm-1's backward - zeros for the rows that were keys / values only - through the freed dO buffer
-                ops.attn_bwd(self.qkv[i], self.tiles_bwd, self.H, self.att[i], self.datt, self.lse[i], self.delta, self.dqkv, lq=self.lq)
-                ops.expand_rows(None, self.q_compact, self.dqkv, M, cols=self.D)
-                ops.expand_rows(dbm, self.q_compact, self.datt, M)
-            elif self.tiles_bwd.ntiles:
-                ops.attn_bwd(self.qkv[i], self.tiles_bwd, self.H, self.att[i], self.datt, self.lse[i], self.delta, self.dqkv, **a8)
-            for sq in self.fused_bwd:
-                ops.attn_bwd_fused(self.qkv[i], sq, self.H, self.att[i], self.datt, self.lse[i], self.dqkv, **a8)
-            # qkv
-            if excl:
-                side.join()
-            if f8b:
-                self._dgrad_fp8(i, "dqkv", "qkv", self.dqkv, self.dqkv8, bp.qkv, b2.qkv if b2 else None, split, self.dln)
-            else:
-                ops.gemm_nt(self.dqkv, bp.qkv.wt, self.dln, M, dual=(split, b2.qkv.wt, None, None) if b2 is not None else None)
-            wgrads(i, "dqkv", (self.dqkv, self.ln1[i], "qkv"))
-            if not excl:
-                side.before_write("dbo")
+    def _dgrad(self, c, i, name, dy, out, M):
+        """(hook) input-gradient GEMM of block i's Linear `name` over M rows: out = dy @ W, both weight sets in one launch.
+        fc2: times the gelu'(x) fc1 saved, + the fc1 bias gradient as the epilogue's column sum (not in deterministic mode)"""
+        bp, b2 = c.blocks[i], c.blocks2[i] if c.blocks2 is not None else None
+        if name != "fc2":
+            ops.gemm_nt(dy, getattr(bp, name).wt, out, M, dual=(c.split, getattr(b2, name).wt, None, None) if b2 is not None else None)
+            return
+        ops.gemm_nt(dy, bp.fc2.wt, out, M, aux=self.fc1[i], act=2, colsum=None if c.det else bp.fc1.gb,
+                    dual=(c.split, b2.fc2.wt, None, None if c.det else b2.fc1.gb) if b2 is not None else None)
+
+    def _ln_bwd_copy(self, blk, name, lo):
+        """(hook) what a LayerNorm backward is passed to also write an 8-bit copy, from row lo, of the gradient `name` (dbo | dbm) of block blk"""
+        return _NO_COPY
+
+    def _attn_bwd_copy(self, i):
+        """(hook) the same for the attention backward kernels and dqkv"""
+        return _NO_COPY
+
+    def _block_backward(self, c, i):
+        if i < self.nrecomp:
+            if not isinstance(c.side, _Inline):      # from here down the blocks share one set of activation buffers: one stream
+                c.side.join()
+                if c.excl and i + 1 < self.nblocks:
+                    self._block_done(c, i + 1)
+                c.side, c.excl, c.grp = _Inline(), False, True
+            self._block_forward(i, c.blocks[i], c.blocks2[i] if c.blocks2 is not None else None, c.split, last_gemm=False)
+        pruned = bool(self.lq) and i == self.nblocks - 1        # the block's upper half (proj ... fc2) lives on the compact rows [0, Mq)
+        assert not pruned or (c.blocks2 is None and c.g16)
+        self._mlp_backward(c, i, pruned)
+        self._attn_backward(c, i, pruned)
+
+    def _mlp_backward(self, c, i, pruned):
+        """fc2, fc1 and LayerNorm-2 of block i: d(x[i + 1]) in dxb[0] (and dx[0]) -> d(xmid) in dxb[1] (and dx[1])"""
+        side, grp, st = c.side, c.grp, self.stats[i]
+        dxo, dxm = self.dx
+        dbo, dbm = self.dxb
+        Mu = self.Mq if pruned else self.rows
+        ranges, rows = ([(0, Mu, c.blocks)], Mu) if pruned else (c.ranges, None)
+        # fc2: d(gelu out) fused with GELU' -> d(fc1 pre-activation)
+        if c.excl:
+            side.join()
+            if i + 1 < self.nblocks:
+                self._block_done(c, i + 1)     # its last wgrad (qkv) was the side stream's tail; fc2's bias came from this LN backward
+        else:
+            side.before_write("dfc1")
+        self._dgrad(c, i, "fc2", dbo, self.dfc1, Mu)
+        if c.det:                 # deterministic mode: the fc1 bias gradient by the column-sum kernel (one writer per element) instead of the epilogue's atomics
             for lo, hi, bl in ranges:
-                # qkv bias gradient: only the query third needs the dqkv matrix.  value third = column sum of dO = (proj bias
-                # gradient, complete since this block's LayerNorm-2 backward) . W_proj; key third = 0 exactly (ops.vecmat)
-                D = self.D
-                ops.colsum(self.dqkv[lo:, :D], bl[i].qkv.gb[:D], hi - lo)
-                # (the vector-matrix product reads the WHOLE accumulated proj bias gradient: a second backward over the same block
-                #  between two zero-fills must say accumulate=True, or the value third would be counted twice - ADVICE r3)
-                #  - checked at the top of this method)
-                if vm_batch is None:
-                    ops.vecmat(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * D:])
-                d8, q8_ = g8rec(i - 1, "dbo")          # the block below reads this gradient through its fc2 input-gradient GEMM
-                _ln_bwd(self.dln[lo:], self.x[i][lo:], st[0][lo:], st[1][lo:], bl[i].n1, None if g16 and i > 0 else dxo[lo:], self.lnws,
-                        hi - lo, None if one else self.row_mod, dres=(self.datt if pruned else dbm if g16 else dxm)[lo:], dx_bf16=dbo[lo:],
-                        dcol=bl[i - 1].fc2.gb if i > 0 else None, dx8=d8[lo:] if d8 is not None else None, q8=q8_, batch=ln_batch)
-        side.join()
-        if ln_batch is not None:
-            ln_batch.finish()          # (before the value thirds: they read the complete proj bias gradients, which are LayerNorm-2 column sums)
-        if vm_batch is not None:
-            vm_batch.run()
-        for j in reversed(range(self.nblocks)):        # (mode 2 has reported all but block 0 on the way)
-            block_done(j)
+                ops.colsum(self.dfc1[lo:], bl[i].fc1.gb, hi - lo)
+        if not grp:
+            self._wgrads(c, i, "dbo", (dbo, self.act[i], "fc2"), rows=rows)
+        if i == self.nblocks - 1 and not c.last_fc2_bias_done:
+            for lo, hi, bl in ranges:
+                ops.colsum(dbo[lo:], bl[i].fc2.gb, hi - lo)
+        # fc1
+        self._dgrad(c, i, "fc1", self.dfc1, self.dln, Mu)
+        if not grp:
+            self._wgrads(c, i, "dfc1", (self.dfc1, self.ln2[i], "fc1"), rows=rows)
+            side.before_write("dbm")
+        for lo, hi, bl in ranges:
+            if c.accumulate:          # value third of the qkv bias gradient (_attn_backward): minus what proj.gb holds before this block adds to it
+                ops.vecmat(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * self.D:], -1.0)
+            _ln_bwd(self.dln[lo:], self.xmid[i][lo:], st[2][lo:], st[3][lo:], bl[i].n2, None if c.g16 else dxm[lo:], self.lnws, hi - lo,
+                    None if c.one else self.row_mod, dres=(dbo if c.g16 else dxo)[lo:], dx_bf16=dbm[lo:], dcol=bl[i].proj.gb,
+                    batch=c.ln_batch, **self._ln_bwd_copy(i, "dbm", lo))
+
+    def _attn_backward(self, c, i, pruned):
+        """proj, attention, qkv and LayerNorm-1 of block i: d(xmid) in dxb[1] (and dx[1]) -> d(x[i]) in dxb[0] (and dx[0])"""
+        side, excl, st, M, D = c.side, c.excl, self.stats[i], self.rows, self.D
+        dxo, dxm = self.dx
+        dbo, dbm = self.dxb
+        rows = self.Mq if pruned else None
+        # proj
+        self._dgrad(c, i, "proj", dbm, self.datt, rows or M)
+        if c.grp:                 # the three wgrads whose operands exist now run beside the attention backward
+            self._wgrads(c, i, "blockA", (dbo, self.act[i], "fc2"), (self.dfc1, self.ln2[i], "fc1"), (dbm, self.att[i], "proj"), rows=rows)
+        else:
+            self._wgrads(c, i, "dbm", (dbm, self.att[i], "proj"), rows=rows)
+            side.before_write("dqkv")
+        copy = self._attn_bwd_copy(i)
+        if pruned:
+            # queries: the first lq rows of every sequence (out / dO compact); dk, dv for every row.  The query third of the other rows of dqkv
+            # is zero by definition (they asked nothing), and the residual gradient of the compact rows goes back into the packed numbering
+            # for LayerNorm-1's backward - zeros for the rows that were keys / values only - through the freed dO buffer
+            ops.attn_bwd(self.qkv[i], self.tiles_bwd, self.H, self.att[i], self.datt, self.lse[i], self.delta, self.dqkv, lq=self.lq)
+            ops.expand_rows(None, self.q_compact, self.dqkv, M, cols=D)
+            ops.expand_rows(dbm, self.q_compact, self.datt, M)
+        elif self.tiles_bwd.ntiles:
+            ops.attn_bwd(self.qkv[i], self.tiles_bwd, self.H, self.att[i], self.datt, self.lse[i], self.delta, self.dqkv, **copy)
+        for sq in self.fused_bwd:
+            ops.attn_bwd_fused(self.qkv[i], sq, self.H, self.att[i], self.datt, self.lse[i], self.dqkv, **copy)
+        # qkv
+        if excl:
+            side.join()
+        self._dgrad(c, i, "qkv", self.dqkv, self.dln, M)
+        self._wgrads(c, i, "dqkv", (self.dqkv, self.ln1[i], "qkv"))
+        if not excl:
+            side.before_write("dbo")
+        for lo, hi, bl in c.ranges:
+            # qkv bias gradient: only the query third needs the dqkv matrix.  value third = column sum of dO = (proj bias
+            # gradient, complete since this block's LayerNorm-2 backward) . W_proj; key third = 0 exactly (ops.vecmat)
+            ops.colsum(self.dqkv[lo:, :D], bl[i].qkv.gb[:D], hi - lo)
+            # (the vector-matrix product reads the WHOLE accumulated proj bias gradient: a second backward over the same block
+            #  between two zero-fills must say accumulate=True, or the value third would be counted twice - ADVICE r3; _claim_epoch)
+            if c.vm_batch is None:
+                ops.vecmat(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * D:])
+            # (the 8-bit copy: the block below reads this gradient through its fc2 input-gradient GEMM)
+            _ln_bwd(self.dln[lo:], self.x[i][lo:], st[0][lo:], st[1][lo:], bl[i].n1, None if c.g16 and i > 0 else dxo[lo:], self.lnws,
+                    hi - lo, None if c.one else self.row_mod, dres=(self.datt if pruned else dbm if c.g16 else dxm)[lo:], dx_bf16=dbo[lo:],
+                    dcol=bl[i - 1].fc2.gb if i > 0 else None, batch=c.ln_batch, **self._ln_bwd_copy(i - 1, "dbo", lo))
 
 
 class PatchEmbedder:
@@ -964,7 +796,7 @@ class ContrastivePass:
         rows = self.rows_a + self.rows_v
         self.rows = rows
         row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-        self.stack = Stack(dev, rows, D, cfg.num_heads, D * cfg.mlp_ratio, lens_a + lens_v, cfg.depth, row_mod, pool=pool, opts=opts)
+        self.stack = make_stack(dev, rows, D, cfg.num_heads, D * cfg.mlp_ratio, lens_a + lens_v, cfg.depth, row_mod, pool=pool, opts=opts)
         self.blocks = [BlockParams(arena, f"vit_base.blocks.{i}", "_a", "_v") for i in range(cfg.depth)]
         self.final = [Norm(arena, "vit_base.norm_a"), Norm(arena, "vit_base.norm")]
         self.row_src_all, self.row_tok_all = _z((rows,), I32, dev), _z((rows,), I32, dev)
@@ -1187,17 +1019,17 @@ class MaePass:
         self.grouped = self.rows_a % 256 == 0 and opts.group_towers               # (EngineOptions.group_towers False: A/B measurements)
         if self.grouped:
             row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-            self.st_t = Stack(dev, self.rows_a + self.rows_v, D, cfg.num_heads, hid, [ka] * B + [kv] * (B * T), cfg.depth, row_mod, pool=pool, opts=opts)
+            self.st_t = make_stack(dev, self.rows_a + self.rows_v, D, cfg.num_heads, hid, [ka] * B + [kv] * (B * T), cfg.depth, row_mod, pool=pool, opts=opts)
             self.st_a = self.st_v = None
         else:
-            self.st_a = Stack(dev, self.rows_a, D, cfg.num_heads, hid, [ka] * B, cfg.depth, pool=pool, opts=opts)
-            self.st_v = Stack(dev, self.rows_v, D, cfg.num_heads, hid, [kv] * (B * T), cfg.depth, pool=pool, opts=opts)
-        self.st_mm = Stack(dev, B * self.n_enc, D, cfg.num_heads, hid, [self.n_enc] * B, 2, pool=pool, opts=opts)
+            self.st_a = make_stack(dev, self.rows_a, D, cfg.num_heads, hid, [ka] * B, cfg.depth, pool=pool, opts=opts)
+            self.st_v = make_stack(dev, self.rows_v, D, cfg.num_heads, hid, [kv] * (B * T), cfg.depth, pool=pool, opts=opts)
+        self.st_mm = make_stack(dev, B * self.n_enc, D, cfg.num_heads, hid, [self.n_enc] * B, 2, pool=pool, opts=opts)
         # EngineOptions.prune_dead: the decoder's rows are laid out [scored tokens (mask 1) | kept tokens] per sample and the last decoder block, decoder_norm,
         # the prediction heads and the loss run on the scored rows only (Stack q_rows; exact: unscored rows have zero loss and zero gradient, :679-682)
         self.ma, self.mv = La - ka, Lv - kv                                       # scored (masked) tokens per audio sequence / frame
         self.lq = self.ma + T * self.mv
-        self.st_dec = Stack(dev, B * self.Ltot, Dd, cfg.dec_heads, Dd * cfg.mlp_ratio, [self.Ltot] * B, cfg.dec_depth, pool=pool, opts=opts,
+        self.st_dec = make_stack(dev, B * self.Ltot, Dd, cfg.dec_heads, Dd * cfg.mlp_ratio, [self.Ltot] * B, cfg.dec_depth, pool=pool, opts=opts,
                             q_rows=self.lq if opts.prune_dead else 0)
         self.prune = self.st_dec.lq > 0
         self.blk_a = [BlockParams(arena, f"ast_base.blocks.{i}", "") for i in range(cfg.depth)]      # :489

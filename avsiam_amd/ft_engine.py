@@ -17,7 +17,7 @@ import torch
 from . import ops
 from .arena import ParamArena
 from .config import AVSiamConfig
-from .engine import BF16, F32, I32, U8, LN_EPS_BLOCK, LN_EPS_FINAL, BlockParams, Norm, PatchEmbedder, Stack, _ln_fwd, _z
+from .engine import BF16, F32, I32, U8, LN_EPS_BLOCK, LN_EPS_FINAL, BlockParams, Norm, PatchEmbedder, _ln_fwd, _z, make_stack
 
 EVAL_FRAMES = 10        # `for t_idx in range(10)` at cav_mae_base.py:940
 
@@ -61,7 +61,7 @@ class Encoder:
         self.rows = self.rows_a + self.rows_v
         self.blocks, self.final = blocks, final
         row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-        self.stack = Stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, cfg.depth, row_mod, inference=inference,
+        self.stack = make_stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, cfg.depth, row_mod, inference=inference,
                            pool=pool, opts=opts)
         self.emb_a = self.emb_v = None
         if na:
@@ -171,7 +171,7 @@ class FtForward:
             La, Lv, D = cfg.audio_tokens, cfg.video_tokens, cfg.embed_dim
             Lj = La + Lv
             nseq = B * nf
-            st = Stack(dev, nseq * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * nseq, 2, inference=True)
+            st = make_stack(dev, nseq * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * nseq, 2, inference=True)
             b = torch.arange(B).view(B, 1)
             i = torch.arange(La).view(1, La)
             maps_a = [((b * nf + t) * Lj + i).reshape(-1).to(I32).to(dev) for t in range(nf)]

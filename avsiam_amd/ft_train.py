@@ -22,7 +22,7 @@ import torch
 from . import ops
 from .arena import ParamArena
 from .config import AVSiamConfig, EngineOptions
-from .engine import F32, I32, LN_EPS_BLOCK, LN_EPS_FINAL, BlockParams, BufferPool, Norm, Stack, _dx_in, _ln_bwd, _ln_fwd, _z
+from .engine import F32, I32, LN_EPS_BLOCK, LN_EPS_FINAL, BlockParams, BufferPool, Norm, _dx_in, _ln_bwd, _ln_fwd, _z, make_stack
 from .ft_engine import Encoder, Head
 
 OUT, OUT_A, OUT_V = 1, 2, 4          # live-output bits of a backward
@@ -101,7 +101,7 @@ class FtTrain:
             cfg, B, dev = self.cfg, self.B, self.dev
             La, Lv, D = cfg.audio_tokens, cfg.video_tokens, cfg.embed_dim
             Lj = La + Lv
-            st = Stack(dev, B * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * B, 2, opts=self.opts)
+            st = make_stack(dev, B * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * B, 2, opts=self.opts)
             b = torch.arange(B).view(B, 1)
             map_a = (b * Lj + torch.arange(La).view(1, La)).reshape(-1).to(I32).to(dev)
             map_v = (b * Lj + La + torch.arange(Lv).view(1, Lv)).reshape(-1).to(I32).to(dev)

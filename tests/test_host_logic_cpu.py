@@ -291,3 +291,20 @@ def test_model_family_exports_and_per_model_options(monkeypatch):
     with pytest.raises(ValueError):
         models.CAVMAE_BASE(cfg=AVSiamConfig(**small), verbose=False, fp8_mode="1", options=EngineOptions())
     assert models.CAVMAE_LARGE(cfg=vit_large(audio_tokens=128, **small), verbose=False).cfg.embed_dim == 1024
+
+
+def test_fp8_stack_selection_by_mode_and_width():
+    """engine.fp8_applies decides which class engine.make_stack builds: the 8-bit stack (engine_fp8.Fp8Stack) needs the mode AND widths that meet the
+    fp8 GEMM's tile constraints - ViT-B / the decoder / ViT-H qualify, a 192-wide stack stays bf16 under every mode, and mode "0" never qualifies.
+    engine.Stack itself is the bf16 stack: every fp8 flag the model and the tests read off a stack is False on the class."""
+    from avsiam_amd import engine
+    from avsiam_amd.config import EngineOptions
+    from avsiam_amd.engine_fp8 import Fp8Stack
+    for D, hidden in ((768, 3072), (512, 2048), (1280, 5120)):
+        for mode in ("1", "2", "3"):
+            assert engine.fp8_applies(EngineOptions(fp8=mode), D, hidden), (mode, D)
+        assert not engine.fp8_applies(EngineOptions(fp8="0"), D, hidden), D
+    for mode in ("0", "1", "2", "3"):
+        assert not engine.fp8_applies(EngineOptions(fp8=mode), 192, 768), mode
+    assert (engine.Stack.fp8, engine.Stack.fp8_bwd, engine.Stack.fp8_wgrad, engine.Stack.fp8_lean) == (False, False, False, False)
+    assert issubclass(Fp8Stack, engine.Stack) and Fp8Stack.fp8 is True

@@ -534,6 +534,7 @@ def test_batched_reduces_give_the_same_gradients(which):
     tensors the batches form (LayerNorm affines, proj / fc2 biases from the fused column sums, the qkv bias value thirds).  Two backwards per model: the
     table built by the first one is reused by the second."""
     from avsiam_amd.config import EngineOptions
+    from avsiam_amd.engine import Stack
     from avsiam_amd.models import CAVMAE_BASE
     mae = which == "mae"
     cfg = AVSiamConfig(audio_tokens=128, frames=2)
@@ -552,7 +553,7 @@ def test_batched_reduces_give_the_same_gradients(which):
             out[0].backward()
             torch.cuda.synchronize()
         eng = m._engine(which, B)
-        stacks = [st for st in vars(eng).values() if hasattr(st, "_ln_batches") or hasattr(st, "_vm_batches")]
+        stacks = [st for st in vars(eng).values() if isinstance(st, Stack) and (st._ln_batches or st._vm_batches)]       # (both tables are created empty with the stack)
         assert bool(stacks) == batch, (batch, len(stacks))          # the batches exist exactly when the option is on
         res[batch] = (out[0].item(), {k: p.grad.detach().double().cpu() for k, p in m._params.items() if p.grad is not None})
     (l0, g0), (l1, g1) = res[False], res[True]
@@ -578,6 +579,8 @@ def test_bf16_and_fp8_models_live_side_by_side():
     the oracle; the fp8 model holds the fp8 tolerances against the oracle on the calibration step and on the step after it.  With the process-wide
     switch of rounds 3 - 5 the mode set last decided the kernels of every model built afterwards."""
     import random
+    from avsiam_amd.engine import Stack
+    from avsiam_amd.engine_fp8 import Fp8Stack
     from avsiam_amd.models import CAVMAE_BASE
     cfg = AVSiamConfig(audio_tokens=128, frames=2)
     B = 3
@@ -628,11 +631,16 @@ def test_bf16_and_fp8_models_live_side_by_side():
                            whole_cos_min=FP8W_WHOLE_COS, matrix_cos_min=FP8W_MATRIX_COS_MIN)
     eng16, eng8 = m16._engine("contrastive", B), m8._engine("contrastive", B)
     assert not eng16.stack.fp8 and eng8.stack.fp8_wgrad
+    # the bf16 model's stacks are the plain engine.Stack - no 8-bit state at all; the fp8 modes live in the subclass
+    stacks16 = [eng16.stack] + [st for st in vars(m16._engine("mae", B)).values() if isinstance(st, Stack)]
+    assert len(stacks16) >= 4 and all(type(st) is Stack and not hasattr(st, "f8") for st in stacks16)
+    assert isinstance(eng8.stack, Fp8Stack) and isinstance(eng8.stack, Stack)
     assert m8.fp8_saturation_events() == 0 and m16.fp8_state() == {}
     # a structural option can be changed on a live model: the engines are rebuilt, the other model is untouched
     m16.set_options(fp8="1")
     out = run(m16, "mae")
     assert m16._engine("mae", B).st_dec.fp8 and not m16._engine("mae", B).st_dec.fp8_bwd and m8.options.fp8 == "3"
+    assert isinstance(m16._engine("mae", B).st_dec, Fp8Stack)
     assert abs(out[0].item() - refs["mae"][0][0].item()) <= FP8_LOSS_RTOL * abs(refs["mae"][0][0].item())
 
 
