@@ -1010,3 +1010,91 @@ def retrieval_rank(q, g, target=None, topk=0, want_sim=False, ws=None):
     _launch("retrieval_rank", 2.0 * nq * ng * D, "avs_retrieval_rank", q, ldq, nq, g, ldg, ng, D, target, out["rank"], out["ties"], out["target_sim"],
             topk, out.get("topk_idx"), out.get("topk_sim"), out.get("sim"), ng if want_sim else 0, ws, ws.numel(), _stream())
     return out
+
+
+# ---- classification metrics (fine-tuning validation) ----------------------------------------------------------------------------------
+CLS_STATS_TILE = 2048    # csrc/metrics.hip CS_TILE: scores of a class staged in LDS at a time
+CLS_STATS_PPW = 64       # csrc/metrics.hip CS_PPW: positives per workgroup (a chunk; also the unit of ap_sum's summation order)
+CLS_STATS_MAX_N = 1 << 22
+_cls_ws = {}             # (device, stream) -> cached workspace, as _retr_ws.  classification_stats_release() drops them
+
+
+def classification_stats_ws_bytes(S, N, C):
+    return int(_lib.load().avs_cls_stats_ws_bytes(int(S), int(N), int(C)))
+
+
+def classification_stats_release():
+    """free the cached workspaces (about 4 (S + 1.3) N C bytes each: 0.55 GB after a call with 11 sets of 20 000 x 527)"""
+    _cls_ws.clear()
+
+
+def cls_stats_views(buf, S, C):
+    """the five results inside the packed byte buffer of classification_stats (a device tensor or its host copy) -> dict of [S, C] / [S] views"""
+    sc = S * C
+    o_np = 16 * sc
+    o_s = o_np + (4 * sc + 7) // 8 * 8
+    return {"ap_sum": buf[:8 * sc].view(torch.float64).view(S, C), "auc_num": buf[8 * sc:16 * sc].view(torch.int64).view(S, C),
+            "n_pos": buf[o_np:o_np + 4 * sc].view(I32).view(S, C), "n_correct": buf[o_s:o_s + 4 * S].view(I32),
+            "n_nonfinite": buf[o_s + 4 * S:o_s + 8 * S].view(I32)}
+
+
+def classification_stats(scores, target, ws=None):
+    """Exact per-class counts behind mAP / mAUC / acc (utilities/stats.py calculate_stats) of S prediction sets against one target, on the device.
+
+    scores fp32 [N, C] or [S, N, C], target fp32 [N, C] (positives: > 0.5); the class axis is dense, rows (and sets) may be strided views with
+    strides of at least the dense ones.  N <= 2^22.  Returns a dict of device tensors, [S, C] / [S] ([C] / 0-dim for a 2-D `scores`):
+      n_pos int32        P, the positives of the class
+      auc_num int64      sum over positives of 2 #{negatives below} + #{negatives tied}: AUC = auc_num / (2 P (N - P)), exact
+      ap_sum float64     sum over positives of #{positives >= s_i} / #{all >= s_i}: AP = ap_sum / P with tied scores sharing a threshold (sklearn's
+                         definition); the summation order is fixed by the positives' sample indices alone
+      n_correct int32    rows whose first-index argmax equals that of the binarised target row (numpy.argmax semantics)
+      n_nonfinite int32  NaN scores of the set; when it is not 0 the set's other results mean nothing (the call itself does not fault)
+      packed uint8       the buffer the five are views of (cls_stats_views): ONE device-to-host copy fetches everything
+    No host synchronisation.  ws: a uint8 device tensor of at least classification_stats_ws_bytes(S, N, C) bytes; None: a cached one.
+    Deterministic: two calls return identical bytes, and S sets in one call the bytes of S separate calls."""
+    for t, name in ((scores, "classification_stats.scores"), (target, "classification_stats.target")):
+        if not t.is_cuda:
+            raise _lib.AvsiamHipError(f"{name}: tensor must live on the GPU")
+        if t.dtype != F32:
+            raise _lib.AvsiamHipError(f"{name}: expected {F32}, got {t.dtype}")
+    squeeze = scores.dim() == 2
+    if squeeze:
+        scores = scores.unsqueeze(0)
+    if scores.dim() != 3 or target.dim() != 2 or min(scores.shape) < 1 or tuple(scores.shape[1:]) != tuple(target.shape):
+        raise _lib.AvsiamHipError(f"classification_stats: scores {tuple(scores.shape)} and target {tuple(target.shape)}: expected [S, N, C] or [N, C] "
+                                  "and [N, C], none of them empty")
+    if scores.device != target.device:
+        raise _lib.AvsiamHipError(f"classification_stats: scores on {scores.device}, target on {target.device}")
+    S, N, C = scores.shape
+    if N > CLS_STATS_MAX_N:
+        raise _lib.AvsiamHipError(f"classification_stats: N = {N} above {CLS_STATS_MAX_N}")
+    row = scores.stride(1) if N > 1 else C
+    sset = scores.stride(0) if S > 1 else N * C
+    ldt = target.stride(0) if N > 1 else C
+    if scores.stride(2) != 1 or row < C or sset < N * C:
+        raise _lib.AvsiamHipError(f"classification_stats.scores: the class axis must be dense and the row / set strides at least C / N * C (strides {scores.stride()})")
+    if target.stride(1) != 1 or ldt < C:
+        raise _lib.AvsiamHipError(f"classification_stats.target: rows must be dense (strides {target.stride()})")
+    dev = scores.device
+    need = classification_stats_ws_bytes(S, N, C)
+    if need == 0:
+        raise _lib.AvsiamHipError(f"classification_stats: shape S={S} N={N} C={C} is outside what avs_cls_stats accepts")
+    if ws is None:
+        key = (dev, _stream())
+        ws = _cls_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _cls_ws[key] = torch.empty(need, dtype=U8, device=dev)
+    else:
+        _chk(ws, U8, "classification_stats.ws")
+        if ws.numel() < need or ws.device != dev:
+            raise _lib.AvsiamHipError(f"classification_stats.ws: {ws.numel()} bytes on {ws.device}, need {need} on {dev}")
+    # zero-filled: the alignment gap behind n_pos belongs to the bytes a caller may compare or hash
+    packed = torch.zeros(16 * S * C + (4 * S * C + 7) // 8 * 8 + 8 * S, dtype=U8, device=dev)
+    out = cls_stats_views(packed, S, C)
+    # work: the comparisons of the counting pass are data-dependent (N * sum_k P_k); the estimate prices the transposing and argmax passes' bytes
+    _launch("cls_stats", (0.0, 12.0 * S * N * C), "avs_cls_stats", scores, sset, row, S, N, C, target, ldt, out["n_pos"], out["auc_num"], out["ap_sum"],
+            out["n_correct"], out["n_nonfinite"], ws, ws.numel(), _stream())
+    if squeeze:
+        out = {k: v[0] for k, v in out.items()}
+    out["packed"] = packed
+    return out

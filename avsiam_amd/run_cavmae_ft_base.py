@@ -8,7 +8,10 @@ label-smoothed multi-hot labels (the json/wav/mp4 pipeline is out of scope on th
 (with or without the 'module.' prefix) with strict=False (:243-249).  Accepted but not implemented: the augmentation flags (freqm, timem,
 noise, mixup), --wa (weight averaging) and --bal - a warning names each one set to a non-default value; --warmup, distillation weights and
 logging are inert.  Data-parallel runs (world size > 1) are refused.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
-Extensions: --steps-per-epoch / --val-steps (synthetic epoch lengths).
+Extensions: --steps-per-epoch / --val-steps (synthetic epoch lengths); --device-metrics: the validation metrics come from the HIP counting
+kernel and the [N, C] outputs never leave the device (traintest_ft_base.calculate_stats_device; AP then groups tied scores as sklearn does);
+--eval-frames: after training, the reference launcher's multi-frame protocol (:326-369) on the validation clips - the metric of every frame and
+of the mean over the frames, written to exp_dir/mul_frame_res.csv (needs the mm_grad test mode).
 """
 import argparse
 import ast
@@ -71,6 +74,9 @@ def build_parser():
     p.add_argument('--dist_url', default='env://')
     p.add_argument('--steps-per-epoch', dest="steps_per_epoch", default=20, type=int, help="synthetic-data epoch length")
     p.add_argument('--val-steps', dest="val_steps", default=2, type=int, help="synthetic validation batches per epoch")
+    p.add_argument('--device-metrics', dest="device_metrics", action="store_true", help="validation metrics on the device (exact counting kernel)")
+    p.add_argument('--eval-frames', dest="eval_frames", action="store_true",
+                   help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
     return p
 
 
@@ -94,13 +100,15 @@ def main(argv=None):
         raise SystemExit("only synthetic AudioSet-shaped data is supported on this path (see module docstring)")
     if args.ftmode not in ("audioonly", "videoonly", "mm_grad"):
         raise SystemExit(f"--ftmode {args.ftmode}: the trainable modes are audioonly, videoonly and mm_grad")
+    if args.eval_frames and (args.ftmode_test or args.ftmode) != "mm_grad":
+        raise SystemExit("--eval-frames scores the frames of multi-frame clips: it needs the mm_grad test mode (--ftmode_test mm_grad)")
     inert = [f"--{k} {getattr(args, k)}" for k, off in (("mixup", 0), ("wa", False), ("freqm", 0), ("timem", 0), ("noise", False), ("bal", None))
              if getattr(args, k) not in (off, 'None')]
     if inert:
         print("WARNING: not implemented on this path, ignored: " + ", ".join(inert) + " - this run trains without them", flush=True)
     from .config import AVSiamConfig
     from .models import CAVMAEFT_BASE
-    from .traintest_ft_base import SyntheticFtLoader, train
+    from .traintest_ft_base import SyntheticFtLoader, evaluate_frames, train
     cfg = AVSiamConfig()
     model = CAVMAEFT_BASE(label_dim=args.n_class)
     if args.pretrain_path != 'None':
@@ -113,7 +121,10 @@ def main(argv=None):
                                    frames=val_frames)
     os.makedirs(args.exp_dir or ".", exist_ok=True)
     args.exp_dir = args.exp_dir or "."
-    return train(model, train_loader, val_loader, None, args)
+    result = train(model, train_loader, val_loader, None, args)
+    if args.eval_frames:
+        result["frame_res"] = evaluate_frames(model, val_loader, args)
+    return result
 
 
 if __name__ == "__main__":

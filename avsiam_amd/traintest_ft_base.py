@@ -4,10 +4,20 @@
 the three parameter groups, no host sync); ``train`` / ``validate`` keep the reference's signatures and returns, branch draw (:133-160), losses
 (:105-110), schedulers (:91-97), freeze_base (:68-71) and artefacts (models/audio_model.{epoch}.pth, best_audio_model.pth, result.csv).
 Deliberate differences: the reference's stray forward outside autocast (:143, which would also break every mode but mm_grad) is not
-reproduced; metrics (mAP, mAUC, acc) are computed in numpy; data-parallel fine-tuning, weight averaging (--wa) and mixup are not implemented.
+reproduced; data-parallel fine-tuning, weight averaging (--wa) and mixup are not implemented.
+
+Metrics (mAP, mAUC, acc).  ``calculate_stats`` is the host path and the default: numpy on the [N, C] sigmoid outputs copied from the device.
+``calculate_stats_device`` (``validate`` with ``args.device_metrics``) keeps outputs and targets on the device: the HIP counting kernel
+(``ops.classification_stats``) returns exact integer counts per class, one small copy brings them to the host, and the two divisions per class
+happen there in float64.  The two paths define AUC identically; AP differs where scores tie: the device path groups equal scores into one
+threshold - the definition of the reference's sklearn ``average_precision_score`` - while ``_average_precision`` ranks tied scores in sample
+order.  Both give NaN for a class without positives (auc: also without negatives), which ``train`` averages over with ``nanmean``.
+``evaluate_frames`` is the reference launcher's multi-frame protocol (run_cavmae_ft_base.py:326-369): the metric of every frame's predictions
+and of their mean over the frames, from one forward pass and one kernel call, written to exp_dir/mul_frame_res.csv.
 """
 import os
 import random
+import statistics
 import time
 
 import numpy as np
@@ -74,13 +84,50 @@ def calculate_stats(output, target):
             for k in range(target.shape[1])]
 
 
+def _stats_from_counts(n_pos, auc_num, ap_sum, n_correct, N):
+    P = n_pos.astype(np.float64)
+    Nn = N - P
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ap = np.where(P > 0, ap_sum / P, np.nan)
+        auc = np.where((P > 0) & (Nn > 0), auc_num.astype(np.float64) / (2.0 * P * Nn), np.nan)
+    acc = float(n_correct) / N
+    return [{"AP": float(ap[k]), "auc": float(auc[k]), "acc": acc} for k in range(len(P))]
+
+
+def calculate_stats_device(output, target):
+    """calculate_stats without leaving the device: output fp32 [N, C] (or [S, N, C]: S prediction sets against one target) and target
+    [N, C] are device tensors; -> the same list of {'AP', 'auc', 'acc'} per class (a list of S such lists for a 3-D output).
+    AP = ap_sum / P and auc = auc_num / (2 P Nn) in float64 from the kernel's counts (ops.classification_stats), after ONE device-to-host copy
+    of the packed per-class results.  AP is NaN for P = 0, auc for P = 0 or Nn = 0 - this module's convention, as calculate_stats.  Equal
+    scores share one threshold in AP (sklearn's definition; see the module docstring).  A NaN among the outputs raises ValueError."""
+    from . import ops
+    res = ops.classification_stats(output.float(), target.float())
+    S = 1 if output.dim() == 2 else output.shape[0]
+    N, C = target.shape
+    h = {k: v.numpy() for k, v in ops.cls_stats_views(res["packed"].cpu(), S, C).items()}
+    if h["n_nonfinite"].any():
+        raise ValueError(f"calculate_stats_device: {int(h['n_nonfinite'].sum())} NaN value(s) among the outputs (per set: {h['n_nonfinite'].tolist()})")
+    sets = [_stats_from_counts(h["n_pos"][s], h["auc_num"][s], h["ap_sum"][s], h["n_correct"][s], N) for s in range(S)]
+    return sets[0] if output.dim() == 2 else sets
+
+
+def stats_summary(stats):
+    """-> {'mAP', 'mAUC', 'd_prime', 'acc'} of a per-class stats list: nan-means over the classes, d' = sqrt(2) * Phi^-1(mAUC) (the reference's
+    utilities.stats.d_prime; NaN where mAUC is not inside (0, 1))."""
+    mAP = float(np.nanmean([s["AP"] for s in stats]))
+    mAUC = float(np.nanmean([s["auc"] for s in stats]))
+    d = statistics.NormalDist().inv_cdf(mAUC) * np.sqrt(2.0) if 0.0 < mAUC < 1.0 else float("nan")
+    return {"mAP": mAP, "mAUC": mAUC, "d_prime": float(d), "acc": stats[0]["acc"]}
+
+
 def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     """validate of the reference (:292-350): no-grad forward in args.ftmode_test with is_eval=True (mm_grad: one joint logit row per frame of
     10-frame clips), loss = args.loss on the mean over dim 1 per batch, sigmoid of the outputs, stats of their mean over dim 1.
     -> (stats, loss), or (stats, sigmoid outputs, targets) with output_pred - as the reference.
     Differences, deliberate: args.ftmode_test None (the launchers do not pass it; the reference would then select no mode and fail) falls back to
     args.ftmode; a two-dimensional output (videoonly with one frame squeezes its frame axis, :865) gets that axis back before the mean, where
-    the reference would average over the classes; one process only (no distributed_concat)."""
+    the reference would average over the classes; one process only (no distributed_concat).  args.device_metrics (absent: False): the stats
+    come from calculate_stats_device, and no [N, C] tensor is copied to the host."""
     device = audio_model.arena.p.device
     mode = getattr(args, "ftmode_test", None) or args.ftmode
     loss_fn = torch.nn.BCEWithLogitsLoss() if args.loss == "BCE" else torch.nn.CrossEntropyLoss()
@@ -97,10 +144,34 @@ def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     loss = float(torch.stack(losses).mean()) if losses else float("nan")
     audio_output = torch.sigmoid(torch.cat(outs).float())
     target = torch.cat(tgts).float()
-    stats = calculate_stats(audio_output.mean(dim=1).cpu().numpy(), target.cpu().numpy())
+    if getattr(args, "device_metrics", False):
+        stats = calculate_stats_device(audio_output.mean(dim=1), target)
+    else:
+        stats = calculate_stats(audio_output.mean(dim=1).cpu().numpy(), target.cpu().numpy())
     if output_pred:
         return stats, audio_output, target
     return stats, loss
+
+
+def evaluate_frames(audio_model, loader, args):
+    """The multi-frame evaluation of the reference's launcher (run_cavmae_ft_base.py:326-369): args.metrics ('mAP' or 'acc') of every
+    frame's predictions, then of the ensemble - the mean of the sigmoid outputs over the frames.  One validate(..., output_pred=True) pass in
+    the multi-frame test mode gives the outputs [N, F, C]; ONE ops.classification_stats call scores the F + 1 prediction sets.
+    -> list of F + 1 floats, also written to exp_dir/mul_frame_res.csv.
+    Differences, deliberate: the reference runs one pass over the data per frame and applies a second sigmoid (or a softmax) to outputs that
+    validate already passed through one; here the sigmoid outputs are scored as they are.  mAP is the nan-mean over the classes."""
+    _, out, target = validate(audio_model, loader, None, args, output_pred=True)
+    if out.dim() != 3 or out.shape[1] < 2:
+        raise ValueError(f"evaluate_frames: expected per-frame outputs [N, F, C] with F > 1, got {tuple(out.shape)} (test mode mm_grad with multi-frame clips)")
+    sets = torch.cat([out.permute(1, 0, 2), out.mean(dim=1).unsqueeze(0)]).contiguous()
+    metric = getattr(args, "metrics", "mAP")
+    res = [s[0]["acc"] if metric == "acc" else float(np.nanmean([c["AP"] for c in s])) for s in calculate_stats_device(sets, target)]
+    for f, r in enumerate(res[:-1]):
+        print(f"{metric} of frame {f} is {r:.4f}", flush=True)
+    print(f"multi-frame {metric} is {res[-1]:.4f}", flush=True)
+    os.makedirs(args.exp_dir, exist_ok=True)
+    np.savetxt(os.path.join(args.exp_dir, "mul_frame_res.csv"), res, delimiter=",")
+    return res
 
 
 class SyntheticFtLoader:

@@ -410,6 +410,29 @@ size_t avs_retrieval_rank_ws_bytes(int nq, int ng, int topk);
 int avs_cls_loss(const float* x, long long ldx, const float* y, long long ldy, int n, int L, int kind, const float* gout, float weight,
                  float* row_loss, float* loss, float* dx, long long ldd, avs_stream_t stream);
 
+/* ---- classification metrics of the fine-tuning loop (src/utilities/stats.py calculate_stats: sklearn's average_precision_score and
+ * roc_auc_score per class, top-1 accuracy) by integer counting, without a sort and without leaving the device.
+ * scores fp32 [S, N, C]: S prediction sets that share one target (element (s, i, k) at s * set_stride + i * row_stride + k; row_stride >= C,
+ * set_stride >= N * C, ignored when S == 1); target fp32 [N, C] (row stride ldt >= C); the positives of class k are target[i][k] > 0.5f.
+ * Comparison is IEEE fp32 order / equality (-0 == +0, infinities are ordinary values).  Per (set, class), [S, C]:
+ *   n_pos    P, the number of positives (Nn = N - P negatives)
+ *   auc_num  the exact integer sum over positives i of 2 #{negatives j: s_j < s_i} + #{negatives j: s_j == s_i};   AUC = auc_num / (2 P Nn)
+ *   ap_sum   fp64 sum over positives i of #{positives j: s_j >= s_i} / #{all j: s_j >= s_i};   AP = ap_sum / P - equal scores share one
+ *            threshold, which is sklearn's definition.  The terms (one correctly rounded fp64 division each) are added in an order that
+ *            depends on nothing but the positives' sample indices: a butterfly over chunks of 64 consecutive positives, the chunks ascending
+ * Per set, [S]:
+ *   n_correct    rows whose first-index argmax of the scores equals the first-index argmax of the binarised (> 0.5f) target row (numpy.argmax
+ *                semantics; a target row without a positive gives class 0)
+ *   n_nonfinite  NaN scores of the set.  A NaN compares false against everything: the call does not fault, the set's other outputs mean nothing
+ * ws: avs_cls_stats_ws_bytes(S, N, C) bytes - the class-major copy of the scores (4 S N C) plus 5 N C for the labels and the positive
+ * lists, plus O(S N C / 64); 0 for a shape the entry refuses.  No floating-point atomics: two calls give identical bytes, S sets in one call the
+ * bytes of S calls.  Argument errors (N, C, S < 1, N or C > 2^22, S > 65534, a stride below the dense one, NULL, ws) return -2 before any
+ * launch.  Cost: N * sum_k ceil(P_k / 64) * 64 comparisons per set. */
+int avs_cls_stats(const float* scores, long long set_stride, long long row_stride, int S, int N, int C, const float* target, long long ldt,
+                  int* n_pos, long long* auc_num, double* ap_sum, int* n_correct, int* n_nonfinite, void* ws, size_t ws_bytes,
+                  avs_stream_t stream);
+size_t avs_cls_stats_ws_bytes(int S, int N, int C);
+
 /* ---- weights: bf16 shadow copies and the fused Adam step (torch.optim.Adam as built at
  * src/traintest_cavmae_base.py:64-66) */
 int avs_transpose_bf16(const avs_bf16* in, avs_bf16* out, int R, int C, avs_stream_t stream);
