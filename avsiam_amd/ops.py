@@ -728,9 +728,16 @@ def colsum(x, out, rows):
     _call("avs_colsum_bf16", x, x.stride(0), out, rows, x.shape[1], _stream())
 
 
+def _chk_vecmat_w(W):
+    """row-major bf16 [K, N] on the GPU, or a column range of a wider one (the kernels take the leading dimension): 8-byte aligned rows"""
+    if not (W.is_cuda and W.dtype == BF16 and W.dim() == 2 and W.stride(1) == 1 and W.stride(0) >= W.shape[1] and W.stride(0) % 4 == 0
+            and W.storage_offset() % 4 == 0):
+        raise _lib.AvsiamHipError("vecmat.W: need a row-major bf16 GPU matrix (or a column range of one, 8-byte aligned)")
+
+
 def vecmat(x, W, y, alpha=1.0):
-    """y[n] += alpha * sum_k x[k] * W[k, n]   (x fp32 [K], W bf16 [K, N], y fp32 [N])"""
-    _chk(x, F32, "vecmat.x"); _chk(W, BF16, "vecmat.W", 2); _chk(y, F32, "vecmat.y")
+    """y[n] += alpha * sum_k x[k] * W[k, n]   (x fp32 [K], W bf16 [K, N], y fp32 [N]); W may be a column range of a wider row-major matrix"""
+    _chk(x, F32, "vecmat.x"); _chk_vecmat_w(W); _chk(y, F32, "vecmat.y")
     K, N = W.shape
     assert x.numel() == K and y.numel() == N and N % 256 == 0 and K % 32 == 0
     _call("avs_vecmat_bf16", x, W, W.stride(0), y, K, N, float(alpha), _stream())
@@ -744,7 +751,7 @@ class VecmatBatch:
 
     def add(self, x, W, y):
         assert self.desc is None, "table already built"
-        _chk(x, F32, "vecmat.x"); _chk(W, BF16, "vecmat.W", 2); _chk(y, F32, "vecmat.y")
+        _chk(x, F32, "vecmat.x"); _chk_vecmat_w(W); _chk(y, F32, "vecmat.y")
         K, N = W.shape
         assert x.numel() == K and y.numel() == N and N % 256 == 0 and K % 32 == 0
         shape = (K, N, W.stride(0))
