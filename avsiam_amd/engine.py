@@ -165,10 +165,18 @@ def _ln_fwd(x, norms, y, mean, rstd, rows, eps, row_mod=None, out_map=None, y8=N
 
 class _LnBatch:
     """The LayerNorm backwards of one stack backward with their parameter-gradient reduces deferred to ONE launch (ops.LnReduceBatch): the first
-    backward allocates a slab workspace per call and collects the table, later ones walk the same calls in the same order."""
+    backward allocates a slab workspace per call and collects the table, later ones walk the same calls in the same order - after check()."""
 
     def __init__(self, D, dev):
-        self.batch, self.dev, self.k, self.keep = ops.LnReduceBatch(D), dev, 0, None
+        self.batch, self.dev, self.k, self.slabs = ops.LnReduceBatch(D), dev, 0, {}
+
+    def check(self):
+        """the table froze one slab count per workspace (self.slabs: by the rows of the call); the kernels write as many as the library's ln_rpw knob
+        says NOW: under another value the one reduce would add stale slabs, or the workspaces would be too small"""
+        for rows, slabs in self.slabs.items():
+            if slabs != ops.layernorm_bwd_slabs(rows):
+                raise RuntimeError(f"a batched LayerNorm reduce was built for {slabs} slabs over {rows} rows and the library now writes another number: "
+                                   "the ln_rpw knob has changed - rebuild the stack (set_options / release_buffers) or restore the knob")
 
     def slot(self, rows, n0, n1, dcol):
         """the workspace of the next LayerNorm backward of this stack backward"""
@@ -176,6 +184,7 @@ class _LnBatch:
         if b.desc is None:
             ws = _z((ops.layernorm_bwd_slabs(rows) * 5 * b.D,), F32, self.dev)
             b.add(ws, rows, n0.dg, n0.db, n1.dg if n1 else None, n1.db if n1 else None, dcol)
+            self.slabs[rows] = b.entries[-1][1]
         else:
             assert self.k < len(b.entries), "a stack's backward issued more LayerNorm backwards than its first one"
         ws = b.keep[self.k][0]
@@ -205,9 +214,9 @@ def _ln_bwd(dy, x, mean, rstd, norms, dx, ws, rows, row_mod=None, out_map=None, 
                       n1.db if n1 else None, row_mod if n1 else None, out_map, dres, dx_bf16, dcol, dx8=dx8, q8=q8)
 
 
-def _dx_in(stack):
-    """fp32 buffer for the gradient a stack's backward STARTS from: only the fp32 gradient stream reads it"""
-    return None if stack.opts.grad_stream == "bf16" else stack.dx[0]
+def _dx_in(stack, lo=0):
+    """fp32 buffer, from row lo, for the gradient a stack's backward STARTS from: only the fp32 gradient stream reads it"""
+    return None if stack.g16 else stack.dx[0][lo:]
 
 
 class _SideStream:
@@ -280,23 +289,27 @@ def fp8_applies(opts, D, hidden):
     return opts.fp8 in ("1", "2", "3") and D % 256 == 0 and hidden % 256 == 0 and D >= 256
 
 
-def make_stack(dev, rows, D, H, hidden, seq_lens, nblocks, row_mod=None, inference=False, pool=None, opts=None, q_rows=0):
+def make_stack(dev, rows, D, H, hidden, seq_lens, blocks, row_mod=None, *, blocks2=None, split=0, inference=False, pool=None, opts=None, q_rows=0):
     """The stack every pass builds (arguments: Stack.__init__): an engine_fp8.Fp8Stack where fp8_applies(), else the bf16 Stack."""
     opts = opts if opts is not None else EngineOptions.from_env()
     cls = Stack
     if fp8_applies(opts, D, hidden):
         from .engine_fp8 import Fp8Stack as cls            # (imported here: engine_fp8 imports this module)
-    return cls(dev, rows, D, H, hidden, seq_lens, nblocks, row_mod, inference=inference, pool=pool, opts=opts, q_rows=q_rows)
+    return cls(dev, rows, D, H, hidden, seq_lens, blocks, row_mod, blocks2=blocks2, split=split, inference=inference, pool=pool, opts=opts, q_rows=q_rows)
 
 
 class Stack:
-    """`nblocks` transformer blocks over a packed [rows, D] fp32 residual stream with saved activations, GEMM operands in bf16.
+    """The transformer blocks `blocks` (BlockParams) over a packed [rows, D] fp32 residual stream with saved activations, GEMM operands in bf16.
+    A stack is bound to its parameters when it is built: forward() and backward() run self.blocks (and self.blocks2 from row self.split).
     Methods marked (hook) are what engine_fp8.Fp8Stack overrides to run the same schedule on 8-bit operands; build stacks with make_stack()."""
 
     fp8 = fp8_bwd = fp8_wgrad = fp8_lean = False          # (the model and the tests ask every stack; Fp8Stack sets them)
 
-    def __init__(self, dev, rows, D, H, hidden, seq_lens, nblocks, row_mod=None, inference=False, pool=None, opts=None, q_rows=0):
-        """inference=True: forward only - no activation is kept, every block reuses one set of buffers (the residual stream
+    def __init__(self, dev, rows, D, H, hidden, seq_lens, blocks, row_mod=None, *, blocks2=None, split=0, inference=False, pool=None, opts=None, q_rows=0):
+        """blocks2 / split: rows [split, rows) run through a SECOND set of blocks (the MAE pass's visual tower next to its audio tower,
+        cav_mae_base.py:487,489) in the same launches - every GEMM takes both weight sets (ops.gemm_nt(dual=...)), the LayerNorm picks the
+        affine per row (row_mod: 0 below split, 1 from it).
+        inference=True: forward only - no activation is kept, every block reuses one set of buffers (the residual stream
         ping-pongs between two) and the backward scratch is not allocated.
         pool (BufferPool): the stack's per-token buffers come from the model's shared activation pool instead of torch.zeros.
         opts (config.EngineOptions): the MODEL's options object, shared by reference - structural fields are read here, runtime fields
@@ -308,8 +321,15 @@ class Stack:
         gradient the backward starts from (dxb[0]) are compact.  `self.lq` says whether the form applies (else 0: plain stack)."""
         assert sum(seq_lens) == rows
         assert pool is None or not inference
+        assert blocks2 is None or (len(blocks2) == len(blocks) and row_mod is not None and 0 < split < rows)
+        nblocks = len(blocks)
+        self.blocks, self.blocks2, self.split = blocks, blocks2, split if blocks2 is not None else 0
+        # what reduces over rows into a parameter gradient runs once per row range (lo, hi, the blocks that own those rows)
+        self.ranges = [(0, rows, blocks)] if blocks2 is None else [(0, split, blocks), (split, rows, blocks2)]
+        self.one = blocks2 is not None               # a row range has ONE affine set; the packed single-tower case selects by row_mod
         self.pool = pool
         self.opts = opts = opts if opts is not None else EngineOptions.from_env()
+        self.g16 = opts.grad_stream == "bf16"        # the residual gradient travels between the LayerNorm backwards in bf16 only
         self._pads = ops.ZeroTable() if pool is not None else None
 
         def _z(shape, dtype, dev_):          # (shadows the module's _z for every allocation below)
@@ -325,7 +345,7 @@ class Stack:
         self.inference = inference
         self.nrecomp = 0 if inference else recompute_blocks(nblocks, opts.recompute)     # blocks [0, nrecomp) keep no activations (one shared set)
         self.recompute = self.nrecomp > 0
-        self._ln_batches, self._vm_batches = {}, {}       # batched reduces of the backward, per (blocks, blocks2, split) it has run with
+        self._ln_batch = self._vm_batch = None            # batched reduces of the backward: built by the first backward that uses them
         self._alloc_operand_copies(_z, dev)
         rp = ops.pad_rows(rows, 128)
         self.rp = rp
@@ -409,11 +429,12 @@ class Stack:
 
     def _setup_pruned(self, q_rows, seq_lens, dev):
         """the pruned last block (Stack.__init__, q_rows): sets self.lq and the row maps where the form applies"""
-        opts, rows, nblocks, row_mod = self.opts, self.rows, self.nblocks, self.row_mod
+        rows, nblocks, row_mod = self.rows, self.nblocks, self.row_mod
         # applies to stacks of equal-length sequences with plain norms, the bf16 gradient stream and the
         # two-kernel attention backward (the decoder: 2 472-token sequences)
-        if (q_rows and row_mod is None and opts.grad_stream == "bf16" and self.tiles.uniform_len and self.tiles_bwd.uniform_len
+        if (q_rows and row_mod is None and self.g16 and self.tiles.uniform_len and self.tiles_bwd.uniform_len
                 and not self.fused_bwd and 0 < q_rows < seq_lens[0] and nblocks >= 1):
+            assert self.blocks2 is None, "the pruned last block has one weight set"
             L, nseq = seq_lens[0], len(seq_lens)
             self.lq, self.Mq = int(q_rows), nseq * int(q_rows)
             c = torch.arange(self.Mq)
@@ -447,58 +468,47 @@ class Stack:
     def out(self):
         return self.x[self.nblocks]
 
-    def forward(self, blocks, blocks2=None, split=0):
-        """blocks2 / split: rows [split, rows) run through a SECOND set of blocks (the MAE pass's visual tower next to its
-        audio tower, cav_mae_base.py:487,489) in the same launches - every GEMM takes both weight sets
-        (ops.gemm_nt(dual=...)), the LayerNorm picks the affine per row (row_mod: 0 below split, 1 from it)."""
+    def forward(self):
         if self._pads is not None:            # pooled buffers: another pass has written over them since this stack last ran
             if self._pads.desc is None and self._pads.entries:
                 self._pads.build(self.x[0].device)
             self._pads.run()
-        self._forward_begin(blocks, blocks2)
-        for i, bp in enumerate(blocks):
-            self._block_forward(i, bp, blocks2[i] if blocks2 is not None else None, split)
+        self._forward_begin()
+        for i in range(self.nblocks):
+            self._block_forward(i)
 
-    def _forward_begin(self, blocks, blocks2):
+    def _forward_begin(self):
         """(hook) in front of the first block of a forward: nothing here"""
 
-    def _block_forward(self, i, bp, b2, split, last_gemm=True):
+    def _block_forward(self, i, last_gemm=True):
         """(hook) Block i: x[i] -> x[i + 1] and everything its backward reads.  last_gemm=False (recompute in front of the backward): x[i + 1]
         is not needed again, the fc2 GEMM is skipped."""
-        M = self.rows
+        M = Mu = self.rows
+        bp, b2 = self.blocks[i], self.blocks2[i] if self.blocks2 is not None else None
         x, st = self.x[i], self.stats[i]
         n1 = bp.n1 if b2 is None else [bp.n1[0], b2.n1[0]]
         n2 = bp.n2 if b2 is None else [bp.n2[0], b2.n2[0]]
+        lq, res_idx = 0, None
         if self.lq and i == self.nblocks - 1:
-            # pruned last block (see __init__): every row is a key / value, the first lq rows of a sequence are the queries; from the attention
-            # output on the block lives on the compact rows
-            assert b2 is None
-            Mq = self.Mq
+            # pruned last block (see __init__; one weight set, no row_mod): every row is a key / value, the first lq rows of a sequence are the
+            # queries; from the attention output on the block lives on the compact rows
             self._qpads.run()
-            _ln_fwd(x, n1, self.ln1[i], st[0], st[1], M, LN_EPS_BLOCK, None)
-            ops.gemm_nt(self.ln1[i], bp.qkv.w, self.qkv[i], M, bias=bp.qkv.b, scale_cols=self.D, col_scale=self.q_scale)
-            ops.attn_fwd(self.qkv[i], self.tiles, self.H, self.att[i], self.lse[i], lq=self.lq)
-            ops.gemm_nt(self.att[i], bp.proj.w, self.xmid[i], Mq, bias=bp.proj.b, res=x, res_idx=self.q_full)
-            _ln_fwd(self.xmid[i], n2, self.ln2[i], st[2], st[3], Mq, LN_EPS_BLOCK, None)
-            ops.gemm_nt(self.ln2[i], bp.fc1.w, self.fc1[i], Mq, bias=bp.fc1.b, out2=self.act[i], act=1)
-            if last_gemm:
-                ops.gemm_nt(self.act[i], bp.fc2.w, self.x[i + 1], Mq, bias=bp.fc2.b, res=self.xmid[i])
-            return
+            Mu, lq, res_idx = self.Mq, self.lq, self.q_full
         dq = dp = d1 = d2 = None
         if b2 is not None:
-            dq, dp = (split, b2.qkv.w, b2.qkv.b, None), (split, b2.proj.w, b2.proj.b, None)
-            d1, d2 = (split, b2.fc1.w, b2.fc1.b, None), (split, b2.fc2.w, b2.fc2.b, None)
+            dq, dp = (self.split, b2.qkv.w, b2.qkv.b, None), (self.split, b2.proj.w, b2.proj.b, None)
+            d1, d2 = (self.split, b2.fc1.w, b2.fc1.b, None), (self.split, b2.fc2.w, b2.fc2.b, None)
         _ln_fwd(x, n1, self.ln1[i], st[0], st[1], M, LN_EPS_BLOCK, self.row_mod)
         ops.gemm_nt(self.ln1[i], bp.qkv.w, self.qkv[i], M, bias=bp.qkv.b, scale_cols=self.D, col_scale=self.q_scale, dual=dq)
-        ops.attn_fwd(self.qkv[i], self.tiles, self.H, self.att[i], self.lse[i])
-        ops.gemm_nt(self.att[i], bp.proj.w, self.xmid[i], M, bias=bp.proj.b, res=x, dual=dp)
-        _ln_fwd(self.xmid[i], n2, self.ln2[i], st[2], st[3], M, LN_EPS_BLOCK, self.row_mod)
-        ops.gemm_nt(self.ln2[i], bp.fc1.w, self.fc1[i], M, bias=bp.fc1.b, out2=self.act[i], act=1, dual=d1)
+        ops.attn_fwd(self.qkv[i], self.tiles, self.H, self.att[i], self.lse[i], lq=lq)
+        ops.gemm_nt(self.att[i], bp.proj.w, self.xmid[i], Mu, bias=bp.proj.b, res=x, res_idx=res_idx, dual=dp)
+        _ln_fwd(self.xmid[i], n2, self.ln2[i], st[2], st[3], Mu, LN_EPS_BLOCK, self.row_mod)
+        ops.gemm_nt(self.ln2[i], bp.fc1.w, self.fc1[i], Mu, bias=bp.fc1.b, out2=self.act[i], act=1, dual=d1)
         if last_gemm:
-            ops.gemm_nt(self.act[i], bp.fc2.w, self.x[i + 1], M, bias=bp.fc2.b, res=self.xmid[i], dual=d2)
+            ops.gemm_nt(self.act[i], bp.fc2.w, self.x[i + 1], Mu, bias=bp.fc2.b, res=self.xmid[i], dual=d2)
 
     # ---- backward: backward() is the schedule of one call; `c` carries the call's arguments and choices to the per-block methods
-    def backward(self, blocks, last_fc2_bias_done=False, blocks2=None, split=0, reducer=None, accumulate=False):
+    def backward(self, last_fc2_bias_done=False, reducer=None, accumulate=False):
         """In: d(out) in self.dxb[0] (bf16) - and in self.dx[0] (fp32) when GRAD_STREAM is "fp32".  Out: d(x[0]) in self.dx[0] (fp32)
         and self.dxb[0].
         reducer (comm.GradReducer, data parallel): told which ranges of the gradient arena are final as the blocks complete.
@@ -507,22 +517,22 @@ class Stack:
         the last block.
         accumulate: the parameter gradients may already hold another pass's contribution (one backward over both passes of a
         combined forward): quantities derived FROM a parameter gradient then use this backward's increment only.
-        blocks2 / split (see forward): the input-gradient GEMMs take both weight sets in one launch; everything that
-        reduces over rows into a parameter gradient (weight-gradient GEMMs, bias column sums, LayerNorm backward with its
-        gamma/beta/bias sums) runs once per row range on row slices of the same buffers."""
+        Two weight sets (blocks2): the input-gradient GEMMs take both in one launch; everything that reduces over rows into a
+        parameter gradient (weight-gradient GEMMs, bias column sums, LayerNorm backward with its gamma/beta/bias sums) runs once
+        per row range (self.ranges) on row slices of the same buffers."""
         assert not self.inference, "Stack(inference=True) keeps no activations"
-        ranges = [(0, self.rows, blocks)] if blocks2 is None else [(0, split, blocks), (split, self.rows, blocks2)]
-        self._claim_epoch(ranges, accumulate)
-        c = SimpleNamespace(blocks=blocks, blocks2=blocks2, split=split, ranges=ranges, reducer=reducer, accumulate=accumulate,
-                            last_fc2_bias_done=last_fc2_bias_done, done=set(), ln_batch=None, vm_batch=None)
-        c.one = blocks2 is not None                  # a row range has ONE affine set; the packed single-tower case selects by row_mod
-        c.side, c.excl, c.grp = self._stream_mode()
-        c.g16 = self.opts.grad_stream == "bf16"      # the residual gradient travels between the LayerNorm backwards in bf16 only
-        c.det = bool(self.opts.deterministic)        # one stream, no epilogue atomics; the library's own reductions follow the "det" knob (the model sets it)
+        det = bool(self.opts.deterministic)          # one stream, no epilogue atomics; the library's own reductions follow the "det" knob (the model sets it)
         # the small per-block reduces in ONE launch each at the end of the stack's backward - unless something wants a block's gradients final as it
         # completes (the data-parallel reducer), the gradients accumulate over two passes, or the deterministic forms are asked for
-        if reducer is None and not accumulate and not c.det and self.opts.batch_reduce:
-            c.ln_batch, c.vm_batch = self._reduce_batches(c)
+        batched = reducer is None and not accumulate and not det and self.opts.batch_reduce
+        if batched and self._ln_batch is not None:
+            self._ln_batch.check()                   # (raises before a gradient epoch is claimed or a kernel of this backward is queued)
+        self._claim_epoch(accumulate)
+        c = SimpleNamespace(reducer=reducer, accumulate=accumulate, last_fc2_bias_done=last_fc2_bias_done, done=set(), det=det,
+                            ln_batch=None, vm_batch=None)
+        c.side, c.excl, c.grp = self._stream_mode()
+        if batched:
+            c.ln_batch, c.vm_batch = self._reduce_batches()
         self._backward_begin(c)
         for i in reversed(range(self.nblocks)):
             self._block_backward(c, i)
@@ -534,19 +544,17 @@ class Stack:
         for j in reversed(range(self.nblocks)):        # (mode 2 has reported all but block 0 on the way)
             self._block_done(c, j)
 
-    def _claim_epoch(self, ranges, accumulate):
+    def _claim_epoch(self, accumulate):
         """a second backward over a block since its gradients were zeroed must say accumulate=True (the value third of the qkv bias gradient is
         a vector-matrix product of the WHOLE accumulated proj bias gradient) - checked before any kernel is queued, so a refused call
         leaves the gradient arena untouched"""
-        for lo_, hi_, bl in ranges:
-            for i in range(self.nblocks):
-                ar = bl[i].arena
-                if not accumulate and ar.gb_epoch.get(bl[i].prefix) == ar.zero_epoch:
-                    raise RuntimeError(f"{bl[i].prefix}: second backward over this block since its gradients were zeroed - pass accumulate=True "
-                                       "(or zero the gradients with arena.zero_grad_range)")
-        for lo_, hi_, bl in ranges:
-            for i in range(self.nblocks):
-                bl[i].arena.gb_epoch[bl[i].prefix] = bl[i].arena.zero_epoch
+        owned = [bp for lo_, hi_, bl in self.ranges for bp in bl]
+        for bp in owned:
+            if not accumulate and bp.arena.gb_epoch.get(bp.prefix) == bp.arena.zero_epoch:
+                raise RuntimeError(f"{bp.prefix}: second backward over this block since its gradients were zeroed - pass accumulate=True "
+                                   "(or zero the gradients with arena.zero_grad_range)")
+        for bp in owned:
+            bp.arena.gb_epoch[bp.prefix] = bp.arena.zero_epoch
 
     def _stream_mode(self):
         """(side, excl, grp) of one backward (_SideStream).  side: where the weight-gradient GEMMs run; excl (mode 2): beside the attention /
@@ -561,22 +569,20 @@ class Stack:
         side = _side_stream(self.dx[0].device) if mode in ("1", "2") else _Inline()
         return side, mode == "2", mode in ("2", "0")
 
-    def _reduce_batches(self, c):
+    def _reduce_batches(self):
         """(ln_batch, vm_batch): the parameter-gradient reduces of the LayerNorm backwards (_LnBatch) and the value thirds of the blocks' qkv bias
         gradients (a [D] x [D, D] product each, _attn_backward) as one launch each instead of one ~10-us launch per block"""
-        key, dev = (id(c.blocks), id(c.blocks2), c.split), self.dx[0].device
-        if key not in self._ln_batches:
-            self._ln_batches[key] = (_LnBatch(self.D, dev), c.blocks, c.blocks2)
-        ln_batch = self._ln_batches[key][0]
-        ln_batch.k = 0
-        if key not in self._vm_batches:
-            vb = ops.VecmatBatch()
-            for lo_, hi_, bl in c.ranges:
-                for i in range(self.nblocks):
-                    vb.add(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * self.D:])
-            vb.build(dev)
-            self._vm_batches[key] = (vb, c.blocks, c.blocks2)                # (the parameter lists are kept alive with their id()s)
-        return ln_batch, self._vm_batches[key][0]
+        dev = self.dx[0].device
+        if self._ln_batch is None:
+            self._ln_batch = _LnBatch(self.D, dev)
+        self._ln_batch.k = 0
+        if self._vm_batch is None:
+            self._vm_batch = ops.VecmatBatch()
+            for lo_, hi_, bl in self.ranges:
+                for bp in bl:
+                    self._vm_batch.add(bp.proj.gb, bp.proj.w, bp.qkv.gb[2 * self.D:])
+            self._vm_batch.build(dev)
+        return self._ln_batch, self._vm_batch
 
     def _block_done(self, c, j):
         """Every kernel writing block j's parameter gradients is queued on the current stream or joined into it."""
@@ -584,16 +590,15 @@ class Stack:
             return
         c.done.add(j)
         if c.reducer is not None:
-            for bl in (c.blocks, c.blocks2):
-                if bl is not None:
-                    for a, b in bl[j].ranges:
-                        c.reducer.ready(a, b)
+            for lo_, hi_, bl in self.ranges:
+                for a, b in bl[j].ranges:
+                    c.reducer.ready(a, b)
 
     def _wgrads(self, c, blk, key, *jobs, rows=None):
         """Weight gradients (gradient, layer input, Linear) of block blk on c.side; the jobs of one call share their token rows.
         rows: the jobs' token rows when they are not the stack's (the pruned last block's compact rows)"""
         def fn():
-            for lo, hi, bl in (c.ranges if rows is None else [(0, rows, c.blocks)]):
+            for lo, hi, bl in (self.ranges if rows is None else [(0, rows, self.blocks)]):
                 self._wgrad(blk, jobs, bl, lo, hi)
         c.side.run(key, fn)
 
@@ -612,12 +617,12 @@ class Stack:
     def _dgrad(self, c, i, name, dy, out, M):
         """(hook) input-gradient GEMM of block i's Linear `name` over M rows: out = dy @ W, both weight sets in one launch.
         fc2: times the gelu'(x) fc1 saved, + the fc1 bias gradient as the epilogue's column sum (not in deterministic mode)"""
-        bp, b2 = c.blocks[i], c.blocks2[i] if c.blocks2 is not None else None
+        bp, b2 = self.blocks[i], self.blocks2[i] if self.blocks2 is not None else None
         if name != "fc2":
-            ops.gemm_nt(dy, getattr(bp, name).wt, out, M, dual=(c.split, getattr(b2, name).wt, None, None) if b2 is not None else None)
+            ops.gemm_nt(dy, getattr(bp, name).wt, out, M, dual=(self.split, getattr(b2, name).wt, None, None) if b2 is not None else None)
             return
         ops.gemm_nt(dy, bp.fc2.wt, out, M, aux=self.fc1[i], act=2, colsum=None if c.det else bp.fc1.gb,
-                    dual=(c.split, b2.fc2.wt, None, None if c.det else b2.fc1.gb) if b2 is not None else None)
+                    dual=(self.split, b2.fc2.wt, None, None if c.det else b2.fc1.gb) if b2 is not None else None)
 
     def _ln_bwd_copy(self, blk, name, lo):
         """(hook) what a LayerNorm backward is passed to also write an 8-bit copy, from row lo, of the gradient `name` (dbo | dbm) of block blk"""
@@ -634,9 +639,8 @@ class Stack:
                 if c.excl and i + 1 < self.nblocks:
                     self._block_done(c, i + 1)
                 c.side, c.excl, c.grp = _Inline(), False, True
-            self._block_forward(i, c.blocks[i], c.blocks2[i] if c.blocks2 is not None else None, c.split, last_gemm=False)
+            self._block_forward(i, last_gemm=False)
         pruned = bool(self.lq) and i == self.nblocks - 1        # the block's upper half (proj ... fc2) lives on the compact rows [0, Mq)
-        assert not pruned or (c.blocks2 is None and c.g16)
         self._mlp_backward(c, i, pruned)
         self._attn_backward(c, i, pruned)
 
@@ -646,7 +650,7 @@ class Stack:
         dxo, dxm = self.dx
         dbo, dbm = self.dxb
         Mu = self.Mq if pruned else self.rows
-        ranges, rows = ([(0, Mu, c.blocks)], Mu) if pruned else (c.ranges, None)
+        ranges, rows = ([(0, Mu, self.blocks)], Mu) if pruned else (self.ranges, None)
         # fc2: d(gelu out) fused with GELU' -> d(fc1 pre-activation)
         if c.excl:
             side.join()
@@ -671,8 +675,8 @@ class Stack:
         for lo, hi, bl in ranges:
             if c.accumulate:          # value third of the qkv bias gradient (_attn_backward): minus what proj.gb holds before this block adds to it
                 ops.vecmat(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * self.D:], -1.0)
-            _ln_bwd(self.dln[lo:], self.xmid[i][lo:], st[2][lo:], st[3][lo:], bl[i].n2, None if c.g16 else dxm[lo:], self.lnws, hi - lo,
-                    None if c.one else self.row_mod, dres=(dbo if c.g16 else dxo)[lo:], dx_bf16=dbm[lo:], dcol=bl[i].proj.gb,
+            _ln_bwd(self.dln[lo:], self.xmid[i][lo:], st[2][lo:], st[3][lo:], bl[i].n2, None if self.g16 else dxm[lo:], self.lnws, hi - lo,
+                    None if self.one else self.row_mod, dres=(dbo if self.g16 else dxo)[lo:], dx_bf16=dbm[lo:], dcol=bl[i].proj.gb,
                     batch=c.ln_batch, **self._ln_bwd_copy(i, "dbm", lo))
 
     def _attn_backward(self, c, i, pruned):
@@ -707,7 +711,7 @@ class Stack:
         self._wgrads(c, i, "dqkv", (self.dqkv, self.ln1[i], "qkv"))
         if not excl:
             side.before_write("dbo")
-        for lo, hi, bl in c.ranges:
+        for lo, hi, bl in self.ranges:
             # qkv bias gradient: only the query third needs the dqkv matrix.  value third = column sum of dO = (proj bias
             # gradient, complete since this block's LayerNorm-2 backward) . W_proj; key third = 0 exactly (ops.vecmat)
             ops.colsum(self.dqkv[lo:, :D], bl[i].qkv.gb[:D], hi - lo)
@@ -716,8 +720,8 @@ class Stack:
             if c.vm_batch is None:
                 ops.vecmat(bl[i].proj.gb, bl[i].proj.w, bl[i].qkv.gb[2 * D:])
             # (the 8-bit copy: the block below reads this gradient through its fc2 input-gradient GEMM)
-            _ln_bwd(self.dln[lo:], self.x[i][lo:], st[0][lo:], st[1][lo:], bl[i].n1, None if c.g16 and i > 0 else dxo[lo:], self.lnws,
-                    hi - lo, None if c.one else self.row_mod, dres=(self.datt if pruned else dbm if c.g16 else dxm)[lo:], dx_bf16=dbo[lo:],
+            _ln_bwd(self.dln[lo:], self.x[i][lo:], st[0][lo:], st[1][lo:], bl[i].n1, None if self.g16 and i > 0 else dxo[lo:], self.lnws,
+                    hi - lo, None if self.one else self.row_mod, dres=(self.datt if pruned else dbm if self.g16 else dxm)[lo:], dx_bf16=dbo[lo:],
                     dcol=bl[i - 1].fc2.gb if i > 0 else None, batch=c.ln_batch, **self._ln_bwd_copy(i - 1, "dbo", lo))
 
 
@@ -796,8 +800,8 @@ class ContrastivePass:
         rows = self.rows_a + self.rows_v
         self.rows = rows
         row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-        self.stack = make_stack(dev, rows, D, cfg.num_heads, D * cfg.mlp_ratio, lens_a + lens_v, cfg.depth, row_mod, pool=pool, opts=opts)
         self.blocks = [BlockParams(arena, f"vit_base.blocks.{i}", "_a", "_v") for i in range(cfg.depth)]
+        self.stack = make_stack(dev, rows, D, cfg.num_heads, D * cfg.mlp_ratio, lens_a + lens_v, self.blocks, row_mod, pool=pool, opts=opts)
         self.final = [Norm(arena, "vit_base.norm_a"), Norm(arena, "vit_base.norm")]
         self.row_src_all, self.row_tok_all = _z((rows,), I32, dev), _z((rows,), I32, dev)
         self.emb_a = PatchEmbedder(arena, dev, self.rows_a, True, cfg, self.row_src_all[:self.rows_a], self.row_tok_all[:self.rows_a])
@@ -957,7 +961,7 @@ class ContrastivePass:
         x0 = st.x[0]
         self.emb_a.forward(audio, x0[:self.rows_a], xf[0])
         self.emb_v.forward(_fold_frames(imgs, cfg.frames), x0[self.rows_a:], xf[1])
-        st.forward(self.blocks)
+        st.forward()
         _ln_fwd(st.out, self.final, self.yf, self.fstat[0], self.fstat[1], self.rows, LN_EPS_FINAL, st.row_mod)
         B, W, D = self.B, self.world, cfg.embed_dim
         ops.segment_mean_fwd(self.yf, self.seg_start, self.reps, 2 * B, row_map=self.slot_maps[0], max_row=2 * B)   # slot -> sample order
@@ -991,7 +995,7 @@ class ContrastivePass:
         ops.segment_mean_bwd(self.dAV, self.seg_start, self.yf, 2 * B, float(W), row_map=self.slot_maps[1], max_row=2 * N)
         _ln_bwd(self.yf, st.out, self.fstat[0], self.fstat[1], self.final, _dx_in(st), st.lnws, self.rows, st.row_mod,
                 dx_bf16=st.dxb[0], dcol=self.blocks[-1].fc2.gb)
-        st.backward(self.blocks, last_fc2_bias_done=True, reducer=reducer, accumulate=accumulate)
+        st.backward(last_fc2_bias_done=True, reducer=reducer, accumulate=accumulate)
         self.emb_a.backward(st.dx[0][:self.rows_a])
         self.emb_v.backward(st.dx[0][self.rows_a:])
 
@@ -1017,25 +1021,28 @@ class MaePass:
         # structurally identical: when the audio rows end on a 256-row tile boundary they run as ONE packed stack whose GEMMs
         # take both weight sets per launch (8 192 audio rows alone fill 37 % of the chip with 256^2 tiles).  Otherwise two stacks.
         self.grouped = self.rows_a % 256 == 0 and opts.group_towers               # (EngineOptions.group_towers False: A/B measurements)
-        if self.grouped:
-            row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-            self.st_t = make_stack(dev, self.rows_a + self.rows_v, D, cfg.num_heads, hid, [ka] * B + [kv] * (B * T), cfg.depth, row_mod, pool=pool, opts=opts)
-            self.st_a = self.st_v = None
-        else:
-            self.st_a = make_stack(dev, self.rows_a, D, cfg.num_heads, hid, [ka] * B, cfg.depth, pool=pool, opts=opts)
-            self.st_v = make_stack(dev, self.rows_v, D, cfg.num_heads, hid, [kv] * (B * T), cfg.depth, pool=pool, opts=opts)
-        self.st_mm = make_stack(dev, B * self.n_enc, D, cfg.num_heads, hid, [self.n_enc] * B, 2, pool=pool, opts=opts)
-        # EngineOptions.prune_dead: the decoder's rows are laid out [scored tokens (mask 1) | kept tokens] per sample and the last decoder block, decoder_norm,
-        # the prediction heads and the loss run on the scored rows only (Stack q_rows; exact: unscored rows have zero loss and zero gradient, :679-682)
-        self.ma, self.mv = La - ka, Lv - kv                                       # scored (masked) tokens per audio sequence / frame
-        self.lq = self.ma + T * self.mv
-        self.st_dec = make_stack(dev, B * self.Ltot, Dd, cfg.dec_heads, Dd * cfg.mlp_ratio, [self.Ltot] * B, cfg.dec_depth, pool=pool, opts=opts,
-                            q_rows=self.lq if opts.prune_dead else 0)
-        self.prune = self.st_dec.lq > 0
         self.blk_a = [BlockParams(arena, f"ast_base.blocks.{i}", "") for i in range(cfg.depth)]      # :489
         self.blk_v = [BlockParams(arena, f"vit_base.blocks.{i}", "_v") for i in range(cfg.depth)]   # :487
         self.blk_mm = [BlockParams(arena, "mm_layer_1", "_a"), BlockParams(arena, "mm_layer_2", "_a")]   # :699-700
         self.blk_dec = [BlockParams(arena, f"decoder_blocks.{i}", "") for i in range(cfg.dec_depth)]
+        self.st_t = self.st_a = self.st_v = None
+        if self.grouped:
+            row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
+            self.st_t = make_stack(dev, self.rows_a + self.rows_v, D, cfg.num_heads, hid, [ka] * B + [kv] * (B * T), self.blk_a, row_mod,
+                                   blocks2=self.blk_v, split=self.rows_a, pool=pool, opts=opts)
+            self.tower_stacks, on_a, on_v = [self.st_t], (self.st_t, 0, self.rows_a), (self.st_t, self.rows_a, None)
+        else:
+            self.st_a = make_stack(dev, self.rows_a, D, cfg.num_heads, hid, [ka] * B, self.blk_a, pool=pool, opts=opts)
+            self.st_v = make_stack(dev, self.rows_v, D, cfg.num_heads, hid, [kv] * (B * T), self.blk_v, pool=pool, opts=opts)
+            self.tower_stacks, on_a, on_v = [self.st_a, self.st_v], (self.st_a, 0, None), (self.st_v, 0, None)
+        self.st_mm = make_stack(dev, B * self.n_enc, D, cfg.num_heads, hid, [self.n_enc] * B, self.blk_mm, pool=pool, opts=opts)
+        # EngineOptions.prune_dead: the decoder's rows are laid out [scored tokens (mask 1) | kept tokens] per sample and the last decoder block, decoder_norm,
+        # the prediction heads and the loss run on the scored rows only (Stack q_rows; exact: unscored rows have zero loss and zero gradient, :679-682)
+        self.ma, self.mv = La - ka, Lv - kv                                       # scored (masked) tokens per audio sequence / frame
+        self.lq = self.ma + T * self.mv
+        self.st_dec = make_stack(dev, B * self.Ltot, Dd, cfg.dec_heads, Dd * cfg.mlp_ratio, [self.Ltot] * B, self.blk_dec, pool=pool, opts=opts,
+                            q_rows=self.lq if opts.prune_dead else 0)
+        self.prune = self.st_dec.lq > 0
         self.fin_a, self.fin_v = [Norm(arena, "ast_base.norm_a")], [Norm(arena, "vit_base.norm")]   # :495,492
         self.dec_norm = [Norm(arena, "decoder_norm")]
         rows_e = self.rows_a + self.rows_v
@@ -1052,6 +1059,10 @@ class MaePass:
         self.map_a = (b * self.n_enc + torch.arange(ka).view(1, ka)).reshape(-1).to(I32).to(dev)
         bt = torch.arange(B * T).view(B * T, 1)
         self.map_v = ((bt // T) * self.n_enc + ka + (bt % T) * kv + torch.arange(kv).view(1, kv)).reshape(-1).to(I32).to(dev)
+        # the towers as (stack, its rows [lo, hi) of that stack's buffers - hi None: to their padded end -, final Norm, fstat pair, out map, rows,
+        # embedder, blocks): both on the packed stack, or one stack each
+        self.towers = [on_a + (self.fin_a, self.fstat_a, self.map_a, self.rows_a, self.emb_a, self.blk_a),
+                       on_v + (self.fin_v, self.fstat_v, self.map_v, self.rows_v, self.emb_v, self.blk_v)]
         rj = self.st_mm.rp
         self.xj_b = _z((rj, D), BF16, dev)                    # bf16 copy of the mm output (decoder_embed operand)
         self.de = _z((rj, Dd), F32, dev)                      # decoder_embed output
@@ -1197,23 +1208,14 @@ class MaePass:
         if plan is not None:
             self._set_plan(plan)
         self.audio, self.imgs, self.xf = audio, _fold_frames(imgs, T), xf
-        ra = self.rows_a
-        if self.grouped:
-            st = self.st_t
-            self.emb_a.forward(audio, st.x[0][:ra], xf[0])
-            self.emb_v.forward(self.imgs, st.x[0][ra:], xf[1])
-            st.forward(self.blk_a, self.blk_v, ra)
-            out_a, out_v = st.out[:ra], st.out[ra:]
-        else:
-            self.emb_a.forward(audio, self.st_a.x[0], xf[0])
-            self.emb_v.forward(self.imgs, self.st_v.x[0], xf[1])
-            self.st_a.forward(self.blk_a)
-            self.st_v.forward(self.blk_v)
-            out_a, out_v = self.st_a.out, self.st_v.out
+        for st, lo, hi, fin, fstat, omap, rows, emb, blks in self.towers:
+            emb.forward(audio if emb.audio else self.imgs, st.x[0][lo:hi], xf[0 if emb.audio else 1])
+        for st in self.tower_stacks:
+            st.forward()
         xj = self.st_mm.x[0]
-        _ln_fwd(out_a, self.fin_a, xj, self.fstat_a[0], self.fstat_a[1], self.rows_a, LN_EPS_FINAL, out_map=self.map_a)
-        _ln_fwd(out_v, self.fin_v, xj, self.fstat_v[0], self.fstat_v[1], self.rows_v, LN_EPS_FINAL, out_map=self.map_v)
-        self.st_mm.forward(self.blk_mm)
+        for st, lo, hi, fin, fstat, omap, rows, emb, blks in self.towers:
+            _ln_fwd(st.out[lo:hi], fin, xj, fstat[0], fstat[1], rows, LN_EPS_FINAL, out_map=omap)
+        self.st_mm.forward()
         rows_j = B * self.n_enc
         ops.cast_scale(self.st_mm.out, self.xj_b, rows_j * cfg.embed_dim, 1.0)
         ops.gemm_nt(self.xj_b, self.dec_embed.w, self.de, rows_j, bias=self.dec_embed.b)                  # :600
@@ -1221,7 +1223,7 @@ class MaePass:
         ops.unshuffle_fwd(self.de, self.src_row, self.pos_row, self.dmod, self.tok["mask_token"], self.tok["decoder_pos_embed_a"],
                           self.tok["decoder_pos_embed_v"], self.tok["decoder_modality_a"], self.tok["decoder_modality_v"],
                           self.st_dec.x[0], rows_d)
-        self.st_dec.forward(self.blk_dec)
+        self.st_dec.forward()
         # (prune: st_dec.out holds the scored rows only, compact; decoder_norm, the heads and the loss see nothing else)
         _ln_fwd(self.st_dec.out, self.dec_norm, self.dn, self.dn_stat[0], self.dn_stat[1], self.dn_rows_in, LN_EPS_BLOCK, out_map=self.dn_map)
         ops.gemm_nt(self.dn[:self.v_off], self.pred_a.w, self.p_a, self.na_rows, bias=self.pred_a.b)       # :634
@@ -1267,7 +1269,7 @@ class MaePass:
         rows_d = B * self.Ltot
         _ln_bwd(self.ddn, sd.out, self.dn_stat[0], self.dn_stat[1], self.dec_norm, _dx_in(sd), sd.lnws, self.dn_rows_in,
                 out_map=self.dn_map, dx_bf16=sd.dxb[0], dcol=self.blk_dec[-1].fc2.gb)
-        sd.backward(self.blk_dec, last_fc2_bias_done=True, reducer=reducer, accumulate=accumulate)
+        sd.backward(last_fc2_bias_done=True, reducer=reducer, accumulate=accumulate)
         g = self.gtok
         ops.unshuffle_bwd(sd.dx[0], self.src_row, B, T, La, Lv, self.dde, g["decoder_pos_embed_a"], g["decoder_pos_embed_v"],
                           g["mask_token"], g["decoder_modality_a"], g["decoder_modality_v"], row_of_pos=self.row_of_pos)
@@ -1281,20 +1283,12 @@ class MaePass:
             ops.cast_scale(sm.dx[0], sm.dxb[0], rows_j * D, 1.0)
         ops.gemm_tn(self.dde_b, self.xj_b, self.dec_embed.gw, rows_j)
         ops.colsum(self.dde_b, self.dec_embed.gb, rows_j)
-        sm.backward(self.blk_mm, reducer=reducer, accumulate=accumulate)
-        if self.grouped:
-            st, ra = self.st_t, self.rows_a
-            for lo, fin, fstat, omap, rows, blks in ((0, self.fin_a, self.fstat_a, self.map_a, self.rows_a, self.blk_a),
-                                                     (ra, self.fin_v, self.fstat_v, self.map_v, self.rows_v, self.blk_v)):
-                _ln_bwd(sm.dx[0], st.out[lo:], fstat[0], fstat[1], fin, None if self.opts.grad_stream == "bf16" else st.dx[0][lo:], st.lnws, rows,
-                        out_map=omap, dx_bf16=st.dxb[0][lo:], dcol=blks[-1].fc2.gb)
-            st.backward(self.blk_a, last_fc2_bias_done=True, blocks2=self.blk_v, split=ra, reducer=reducer, accumulate=accumulate)
-            self.emb_a.backward(st.dx[0][:ra])
-            self.emb_v.backward(st.dx[0][ra:])
-            return
-        for st, fin, fstat, omap, rows, emb, blks in ((self.st_a, self.fin_a, self.fstat_a, self.map_a, self.rows_a, self.emb_a, self.blk_a),
-                                                      (self.st_v, self.fin_v, self.fstat_v, self.map_v, self.rows_v, self.emb_v, self.blk_v)):
-            _ln_bwd(sm.dx[0], st.out, fstat[0], fstat[1], fin, _dx_in(st), st.lnws, rows, out_map=omap, dx_bf16=st.dxb[0],
-                    dcol=blks[-1].fc2.gb)
-            st.backward(blks, last_fc2_bias_done=True, reducer=reducer, accumulate=accumulate)
-            emb.backward(st.dx[0])
+        sm.backward(reducer=reducer, accumulate=accumulate)
+        for st in self.tower_stacks:
+            mine = [t for t in self.towers if t[0] is st]
+            for st_, lo, hi, fin, fstat, omap, rows, emb, blks in mine:
+                _ln_bwd(sm.dx[0], st.out[lo:], fstat[0], fstat[1], fin, _dx_in(st, lo), st.lnws, rows, out_map=omap, dx_bf16=st.dxb[0][lo:],
+                        dcol=blks[-1].fc2.gb)
+            st.backward(last_fc2_bias_done=True, reducer=reducer, accumulate=accumulate)
+            for st_, lo, hi, fin, fstat, omap, rows, emb, blks in mine:
+                emb.backward(st.dx[0][lo:hi])

@@ -38,17 +38,18 @@ _GRAD_OF = {"fc2": "dbo", "fc1": "dfc1", "proj": "dbm", "qkv": "dqkv"}      # Li
 
 
 class Fp8Stack(Stack):
-    """engine.Stack on 8-bit GEMM operands (module docstring).  fp8_bwd / fp8_wgrad / fp8_lean: modes 2 - 3 / mode 3 / mode 3's 8-bit-only outputs."""
+    """engine.Stack on 8-bit GEMM operands (module docstring).  fp8_bwd / fp8_wgrad / fp8_lean: modes 2 - 3 / mode 3 / mode 3's 8-bit-only outputs.
+    The records, the calibrated sets and the frozen weight tables (w8_batch, wt8_batch) belong to the blocks the stack is built with."""
 
     fp8 = True
 
-    def __init__(self, dev, rows, D, H, hidden, seq_lens, nblocks, row_mod=None, inference=False, pool=None, opts=None, q_rows=0):
+    def __init__(self, dev, rows, D, H, hidden, seq_lens, blocks, row_mod=None, *, blocks2=None, split=0, inference=False, pool=None, opts=None, q_rows=0):
         """arguments: Stack.__init__ (q_rows: the pruned last block is a bf16 form - not applied here)"""
         assert opts is not None and fp8_applies(opts, D, hidden)
         self.fp8_bwd = opts.fp8 in ("2", "3") and not inference
         self.fp8_wgrad = self.fp8_bwd and opts.fp8 == "3"
         self.fp8_lean = self.fp8_wgrad and opts.fp8_lean
-        super().__init__(dev, rows, D, H, hidden, seq_lens, nblocks, row_mod, inference=inference, pool=pool, opts=opts, q_rows=0)
+        super().__init__(dev, rows, D, H, hidden, seq_lens, blocks, row_mod, blocks2=blocks2, split=split, inference=inference, pool=pool, opts=opts, q_rows=0)
 
     # ---- constructor hooks
     def _alloc_operand_copies(self, z, dev):
@@ -131,22 +132,23 @@ class Fp8Stack(Stack):
                 self.g8_seen = {tuple(k) for k in st["grad"]["seen"]}
 
     # ---- forward
-    def _forward_begin(self, blocks, blocks2):
+    def _forward_begin(self):
         self.f8.update()                   # delayed scaling: last forward's amax -> history -> this forward's scales (one launch)
         if self.w8_batch is None and len(self.f8_seen) == 4 * self.nblocks:      # every GEMM calibrated: freeze the weight table
             self.w8_batch = ops.Fp8Batch(self.f8)
-            for i, bp in enumerate(blocks):
+            for i, bp in enumerate(self.blocks):
                 for name in ("qkv", "proj", "fc1", "fc2"):
-                    for st_, bl in enumerate((bp,) if blocks2 is None else (bp, blocks2[i])):
+                    for st_, bl in enumerate((bp,) if self.blocks2 is None else (bp, self.blocks2[i])):
                         self.w8_batch.add(getattr(bl, name).w, self._w8(i, name, st_), (i * 4 + _GEMM[name]) * 3 + 1 + st_)
             self.w8_batch.build(self.x[0].device)
         if self.w8_batch is not None:
             self.w8_batch.run()            # all weights of the stack -> e4m3 with this step's scales (one launch)
 
-    def _block_forward(self, i, bp, b2, split, last_gemm=True):
+    def _block_forward(self, i, last_gemm=True):
         """The block's forward with e4m3 GEMM operands.  Once a GEMM's records are calibrated its activation arrives in e4m3 from the kernel
         that produces it; before that (first use) it is quantised by a pass."""
         M = self.rows
+        bp, b2 = self.blocks[i], self.blocks2[i] if self.blocks2 is not None else None
         x, st = self.x[i], self.stats[i]
         n1 = bp.n1 if b2 is None else [bp.n1[0], b2.n1[0]]
         n2 = bp.n2 if b2 is None else [bp.n2[0], b2.n2[0]]
@@ -156,20 +158,20 @@ class Fp8Stack(Stack):
         lean = self.fp8_lean               # a calibrated consumer reads the e4m3 copy only, and so does its weight gradient: no bf16 output
         _ln_fwd(x, n1, None if lean and seen("qkv") else self.ln1[i], st[0], st[1], M, LN_EPS_BLOCK, self.row_mod, y8=l1 if seen("qkv") else None,
                 q8_dev=r("qkv") if seen("qkv") else None)
-        self._gemm_fp8(i, "qkv", self.ln1[i], l1, bp.qkv, b2.qkv if b2 else None, split, self.qkv[i], scale_cols=self.D, col_scale=self.q_scale)
+        self._gemm_fp8(i, "qkv", self.ln1[i], l1, bp.qkv, b2.qkv if b2 else None, self.qkv[i], scale_cols=self.D, col_scale=self.q_scale)
         ops.attn_fwd(self.qkv[i], self.tiles, self.H, self.att[i], self.lse[i], **({"out8": at8, "q8": r("proj")} if seen("proj") else {}))
-        self._gemm_fp8(i, "proj", self.att[i], at8, bp.proj, b2.proj if b2 else None, split, self.xmid[i], res=x)
+        self._gemm_fp8(i, "proj", self.att[i], at8, bp.proj, b2.proj if b2 else None, self.xmid[i], res=x)
         _ln_fwd(self.xmid[i], n2, None if lean and seen("fc1") else self.ln2[i], st[2], st[3], M, LN_EPS_BLOCK, self.row_mod, y8=l2 if seen("fc1") else None,
                 q8_dev=r("fc1") if seen("fc1") else None)
         # (the fc2 weight gradient reads the e4m3 copy of gelu(x) too: with fp8 weight gradients it is written even when fc2 itself is skipped)
         o8 = {"out8": ac8, "q8": r("fc2")} if (seen("fc2") and (last_gemm or self.fp8_wgrad)) else {}
-        self._gemm_fp8(i, "fc1", self.ln2[i], l2, bp.fc1, b2.fc1 if b2 else None, split, self.fc1[i], out2=None if lean and o8 else self.act[i], act=1, **o8)
+        self._gemm_fp8(i, "fc1", self.ln2[i], l2, bp.fc1, b2.fc1 if b2 else None, self.fc1[i], out2=None if lean and o8 else self.act[i], act=1, **o8)
         if last_gemm:
-            self._gemm_fp8(i, "fc2", self.act[i], ac8, bp.fc2, b2.fc2 if b2 else None, split, self.x[i + 1], res=self.xmid[i])
+            self._gemm_fp8(i, "fc2", self.act[i], ac8, bp.fc2, b2.fc2 if b2 else None, self.x[i + 1], res=self.xmid[i])
         elif self.fp8_wgrad and not seen("fc2"):
             raise RuntimeError("fp8 weight gradients: a recomputed block met an uncalibrated fc2 record")
 
-    def _gemm_fp8(self, i, name, A, a8, lin, lin2, split, out, **kw):
+    def _gemm_fp8(self, i, name, A, a8, lin, lin2, out, **kw):
         """One forward GEMM on e4m3 operands.  a8: where this GEMM's activation lives in e4m3 once its producer writes it."""
         M = self.rows
         W, W2 = lin.w, (lin2.w if lin2 is not None else None)
@@ -194,7 +196,7 @@ class Fp8Stack(Stack):
             ops.quantize_fp8(W, 1.0, out=w8, q=rw)
             if W2 is not None:
                 ops.quantize_fp8(W2, 1.0, out=w8b, q=rw2)
-        dual = (split, w8b, lin2.b, rw2) if W2 is not None else None
+        dual = (self.split, w8b, lin2.b, rw2) if W2 is not None else None
         ops.gemm_nt_fp8(a8, w8, out, M, bias=lin.b, qa=ra, qw=rw, dual=dual, **kw)
 
     # ---- backward (modes 2 / 3; mode 1 keeps the bf16 backward)
@@ -203,7 +205,7 @@ class Fp8Stack(Stack):
             return
         self.g8.update()                   # delayed scaling of the gradient operands: last backward's amax -> this backward's scales
         self.g8_have = set()
-        if self.wt8_batch is None and len(self._wt8_pending) == 4 * self.nblocks * (2 if c.blocks2 is not None else 1):
+        if self.wt8_batch is None and len(self._wt8_pending) == 4 * self.nblocks * len(self.ranges):
             self.wt8_batch = ops.Fp8Batch(self.f8)      # the transposed copies use the forward's weight records (the same tensors)
             for src, dst, ridx in self._wt8_pending:
                 self.wt8_batch.add(src, dst, ridx)
@@ -230,7 +232,7 @@ class Fp8Stack(Stack):
     def _dgrad(self, c, i, name, dy, out, M):
         if not self.fp8_bwd:
             return super()._dgrad(c, i, name, dy, out, M)
-        bp, b2 = c.blocks[i], c.blocks2[i] if c.blocks2 is not None else None
+        bp, b2 = self.blocks[i], self.blocks2[i] if self.blocks2 is not None else None
         kw = {}
         if name == "fc2":                  # GELU' epilogue; the fc1 bias gradient as its column sum (deterministic mode: by the column-sum kernel)
             kw = {"act": 2, "aux": self.fc1[i], "colsum": None if c.det else bp.fc1.gb, "colsum2": None if c.det or b2 is None else b2.fc1.gb}
@@ -240,9 +242,9 @@ class Fp8Stack(Stack):
                 if self.fp8_lean and not c.det:        # once this epilogue writes the e5m2 copy nothing reads the bf16 gradient: no bf16 output
                     out = None                         # (deterministic mode keeps it: the column-sum kernel reads it)
         gname = _GRAD_OF[name]
-        self._dgrad_fp8(i, gname, name, dy, self._grad8[gname], getattr(bp, name), getattr(b2, name) if b2 is not None else None, c.split, out, **kw)
+        self._dgrad_fp8(i, gname, name, dy, self._grad8[gname], getattr(bp, name), getattr(b2, name) if b2 is not None else None, out, **kw)
 
-    def _dgrad_fp8(self, i, gname, wname, A, a8, lin, lin2, split, out, colsum2=None, **kw):
+    def _dgrad_fp8(self, i, gname, wname, A, a8, lin, lin2, out, colsum2=None, **kw):
         """One input-gradient GEMM on an e5m2 gradient operand (A: its bf16 form, a8: where its e5m2 copy lives - written by the
         producer when (i, gname) is in g8_have, else by a pass here) and the e4m3 copy of the transposed weight, quantised with the
         scale of the forward's weight record (the same tensor)."""
@@ -265,7 +267,7 @@ class Fp8Stack(Stack):
             if lin2 is not None:
                 ops.quantize_fp8(lin2.wt, 1.0, out=w8b, q=rw2)
                 self._wt8_pending.append((lin2.wt, w8b, base + 2))
-        dual = (split, w8b, None, rw2, colsum2) if lin2 is not None else None
+        dual = (self.split, w8b, None, rw2, colsum2) if lin2 is not None else None
         ops.gemm_nt_fp8(a8, w8, out, M, qa=rec, qw=rw, grad=True, dual=dual, **kw)
 
     def _wgrad(self, blk, jobs, bl, lo, hi):

@@ -61,7 +61,7 @@ class Encoder:
         self.rows = self.rows_a + self.rows_v
         self.blocks, self.final = blocks, final
         row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-        self.stack = make_stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, cfg.depth, row_mod, inference=inference,
+        self.stack = make_stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, blocks, row_mod, inference=inference,
                            pool=pool, opts=opts)
         self.emb_a = self.emb_v = None
         if na:
@@ -85,7 +85,7 @@ class Encoder:
             self.emb_a.forward(audio, st.x[0][:self.rows_a])
         if self.nv:
             self.emb_v.forward(frames, st.x[0][self.rows_a:])
-        st.forward(self.blocks)
+        st.forward()
         _ln_fwd(st.out, self.final, self.yf, self.fstat[0], self.fstat[1], self.rows, LN_EPS_FINAL, st.row_mod)
 
     def pool(self):
@@ -171,7 +171,7 @@ class FtForward:
             La, Lv, D = cfg.audio_tokens, cfg.video_tokens, cfg.embed_dim
             Lj = La + Lv
             nseq = B * nf
-            st = make_stack(dev, nseq * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * nseq, 2, inference=True)
+            st = make_stack(dev, nseq * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * nseq, self.blk_mm, inference=True)
             b = torch.arange(B).view(B, 1)
             i = torch.arange(La).view(1, La)
             maps_a = [((b * nf + t) * Lj + i).reshape(-1).to(I32).to(dev) for t in range(nf)]
@@ -202,7 +202,7 @@ class FtForward:
         for t in range(nf):                                                        # audio tokens go to every (b, t) sequence
             _ln_fwd(so, fin_a, xj, enc.fstat[0], enc.fstat[1], enc.rows_a, LN_EPS_FINAL, out_map=maps_a[t])
         _ln_fwd(so[enc.rows_a:], fin_v, xj, enc.fstat[0][enc.rows_a:], enc.fstat[1][enc.rows_a:], enc.rows_v, LN_EPS_FINAL, out_map=map_v)
-        st.forward(self.blk_mm)
+        st.forward()
         ops.segment_mean_fwd(st.out, seg_start, pooled, 2 * B * nf)                # [a-part mean | v-part mean] per sequence (:948-951)
         out = self.head_mm.forward(pooled.view(-1, 2 * self.cfg.embed_dim), B * nf)
         if is_eval:

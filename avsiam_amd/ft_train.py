@@ -101,7 +101,7 @@ class FtTrain:
             cfg, B, dev = self.cfg, self.B, self.dev
             La, Lv, D = cfg.audio_tokens, cfg.video_tokens, cfg.embed_dim
             Lj = La + Lv
-            st = make_stack(dev, B * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * B, 2, opts=self.opts)
+            st = make_stack(dev, B * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * B, self.blk_mm, opts=self.opts)
             b = torch.arange(B).view(B, 1)
             map_a = (b * Lj + torch.arange(La).view(1, La)).reshape(-1).to(I32).to(dev)
             map_v = (b * Lj + La + torch.arange(Lv).view(1, Lv)).reshape(-1).to(I32).to(dev)
@@ -149,7 +149,7 @@ class FtTrain:
                 _ln_fwd(so, self.final[:1], st.x[0], enc.fstat[0], enc.fstat[1], enc.rows_a, LN_EPS_FINAL, out_map=j["map_a"])
                 _ln_fwd(so[enc.rows_a:], self.final[1:], st.x[0], enc.fstat[0][enc.rows_a:], enc.fstat[1][enc.rows_a:], enc.rows_v, LN_EPS_FINAL,
                         out_map=j["map_v"])
-                st.forward(self.blk_mm)
+                st.forward()
                 ops.segment_mean_fwd(st.out, j["seg"], j["pooled"], 2 * B)                   # [a-part mean | v-part mean] per clip (:1027-1030)
                 res[OUT] = self.head_mm.forward(j["pooled"].view(-1, 2 * self.cfg.embed_dim), B)
             if heads & (OUT_A | OUT_V):
@@ -214,7 +214,7 @@ class FtTrain:
                 self.head_mm.backward(B, j["dpooled"].view(-1, 2 * D))
                 ops.segment_mean_bwd(j["dpooled"], j["seg"], sm.dx[0], 2 * B)
                 ops.cast_scale(sm.dx[0], sm.dxb[0], sm.rows * D, 1.0)
-                sm.backward(self.blk_mm)
+                sm.backward()
                 dy = sm.dx[0]
                 if not base:
                     return
@@ -229,9 +229,8 @@ class FtTrain:
             ra = enc.rows_a
             for lo, fin, rows, omap in ((0, self.final[:1], ra, maps[0]), (ra, self.final[1:], enc.rows_v, maps[1])):
                 _ln_bwd(dy if omap is not None else dy[lo:], st.out[lo:], enc.fstat[0][lo:], enc.fstat[1][lo:], fin,
-                        None if self.opts.grad_stream == "bf16" else st.dx[0][lo:], st.lnws, rows, out_map=omap, dx_bf16=st.dxb[0][lo:],
-                        dcol=self.blocks[-1].fc2.gb)
-        st.backward(self.blocks, last_fc2_bias_done=True)
+                        _dx_in(st, lo), st.lnws, rows, out_map=omap, dx_bf16=st.dxb[0][lo:], dcol=self.blocks[-1].fc2.gb)
+        st.backward(last_fc2_bias_done=True)
         if enc.na:
             enc.emb_a.backward(st.dx[0][:enc.rows_a])
         if enc.nv:

@@ -553,7 +553,7 @@ def test_batched_reduces_give_the_same_gradients(which):
             out[0].backward()
             torch.cuda.synchronize()
         eng = m._engine(which, B)
-        stacks = [st for st in vars(eng).values() if isinstance(st, Stack) and (st._ln_batches or st._vm_batches)]       # (both tables are created empty with the stack)
+        stacks = [st for st in vars(eng).values() if isinstance(st, Stack) and (st._ln_batch is not None or st._vm_batch is not None)]   # (None until a backward builds them)
         assert bool(stacks) == batch, (batch, len(stacks))          # the batches exist exactly when the option is on
         res[batch] = (out[0].item(), {k: p.grad.detach().double().cpu() for k, p in m._params.items() if p.grad is not None})
     (l0, g0), (l1, g1) = res[False], res[True]
@@ -569,6 +569,58 @@ def test_batched_reduces_give_the_same_gradients(which):
         if e > worst[0]:
             worst = (e, k)
     record_margin(f"batch_reduce_{which}", worst_grad_rel=worst[0], worst_tensor=worst[1])
+    assert worst[0] < 1e-5, worst
+
+
+@pytest.mark.parametrize("ln_rpw", [16, 4])
+def test_batched_reduce_refuses_a_changed_ln_rpw(ln_rpw):
+    """The batched LayerNorm reduce of a stack holds the slab count of every workspace as the library's ln_rpw knob gave it at the first backward
+    (automatic: 8 rows per wave at these row counts).  Under 16 the kernels write half as many slabs and the one reduce would add stale ones; under 4
+    twice as many, more than the workspaces hold.  A backward under a changed knob raises before the stack queues a kernel or claims a gradient
+    epoch, and with the knob restored the same model gives the first backward's gradients again: every tensor to 1e-5 of its norm, the order of the
+    fp32 atomics (test_batched_reduces_give_the_same_gradients: measured 2.7e-7 / 4.5e-7)."""
+    import random
+    from avsiam_amd import _lib
+    from avsiam_amd.models import CAVMAE_BASE
+    cfg = AVSiamConfig(audio_tokens=128, frames=2)
+    B = 5
+    a, v = synth_inputs(cfg, B, 41)
+    gen = torch.Generator().manual_seed(14)
+    plan = make_contrastive_plan(cfg, B, gen, random.Random(11))
+    m = CAVMAE_BASE(cfg=cfg, init_seed=78, init_mode="random", verbose=False, plan_seed=5).cuda()
+
+    def forward():
+        for p in m._params.values():
+            p.grad = None
+        return m(a.cuda(), v.cuda(), mae_loss_weight=0, contrast_loss_weight=0.01, mask_plan=plan)[0]
+
+    def grads():
+        torch.cuda.synchronize()
+        return {k: p.grad.detach().double().cpu() for k, p in m._params.items() if p.grad is not None}
+
+    forward().backward()
+    g0 = grads()
+    assert m._engine("contrastive", B).stack._ln_batch is not None and len(g0) > 100
+    try:
+        _lib.tuning_set("ln_rpw", ln_rpw)
+        loss = forward()
+        with pytest.raises(RuntimeError, match="ln_rpw"):
+            loss.backward()
+    finally:
+        _lib.tuning_set("ln_rpw", 0)
+    forward().backward()
+    g1 = grads()
+    assert g0.keys() == g1.keys()
+    worst = (0.0, None)
+    for k in g0:
+        n0 = float(g0[k].norm())
+        if n0 == 0:
+            assert float(g1[k].norm()) == 0, k
+            continue
+        e = float((g1[k] - g0[k]).norm()) / n0
+        if e > worst[0]:
+            worst = (e, k)
+    print(f"ln_rpw {ln_rpw}: worst gradient tensor after recovery {worst}")
     assert worst[0] < 1e-5, worst
 
 
