@@ -273,3 +273,105 @@ class GradReducer:
     def wait_deferred(self):
         self._wait(self.deferred)
         self.deferred = []
+
+
+def _union(ranges):
+    """sorted, merged [a, b) ranges (overlapping and touching ones joined)"""
+    out = []
+    for a, b in sorted((int(a), int(b)) for a, b in ranges if b > a):
+        if out and a <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], b)
+        else:
+            out.append([a, b])
+    return out
+
+
+def fixed_schedule(units, lo, hi, min_elems=16 << 20):
+    """The message list of a FixedScheduleReducer from a layout: `units` are [a, b) ranges inside [lo, hi) in the order the longest backward
+    completes them.  Consecutive units that touch in memory are joined until a message holds `min_elems`; what no unit covers follows at the
+    end, joined to the last message where it touches it.  -> ordered [a, b) chunks that tile [lo, hi) exactly once.  Depends on the layout
+    alone, so every rank derives the same list."""
+    chunks, cur = [], None
+    for a, b in units:
+        assert lo <= a < b <= hi, "fixed_schedule: unit outside the range"
+        if cur is not None and (a == cur[1] or b == cur[0]):
+            cur = [min(a, cur[0]), max(b, cur[1])]
+        else:
+            if cur is not None:
+                chunks.append(tuple(cur))
+            cur = [a, b]
+        if cur[1] - cur[0] >= min_elems:
+            chunks.append(tuple(cur))
+            cur = None
+    if cur is not None:
+        chunks.append(tuple(cur))
+    covered = _union(chunks)
+    assert sum(b - a for a, b in covered) == sum(b - a for a, b in chunks), "fixed_schedule: units overlap"
+    at = lo
+    for a, b in covered + [[hi, hi]]:
+        if a > at:                                         # a hole no unit claims
+            if chunks and chunks[-1][0] == a:
+                chunks[-1] = (at, chunks[-1][1])
+            elif chunks and chunks[-1][1] == at:
+                chunks[-1] = (chunks[-1][0], a)
+            else:
+                chunks.append((at, a))
+        at = max(at, b)
+    return chunks
+
+
+class FixedScheduleReducer:
+    """All-reduce(SUM) of a gradient range in a message schedule that does not depend on what this rank's backward computes.
+
+    GradReducer sends whenever enough ready elements have piled up: fine while every rank runs the same backward.  In data-parallel
+    fine-tuning each rank draws its own branch (out / out_a / out_v), so the ranks complete different parts of the arena in different orders,
+    and a collective whose message sequence differs between ranks hangs or adds mismatched ranges.  Here the messages are `chunks`, a fixed,
+    ordered list of [a, b) ranges tiling the range exactly once (fixed_schedule); chunk i goes out as soon as it is entirely final on this
+    rank AND chunks 0..i-1 have gone.  ``begin(dead)`` declares the ranges this rank's backward never writes: final from the start (zeros -
+    the caller zeroed the arena).  ``ready(a, b)`` records a final range (any order; overlaps with dead or earlier ranges are harmless).
+    ``finish()`` sends the remaining chunks in order, then `tail` (a small tensor that travels as the schedule's LAST message: the liveness
+    vector), and waits for everything.  fp32 wire only.  `log` lists what was sent since begin(): (a, b) per chunk, ("tail", n) for the tail."""
+
+    def __init__(self, comm, g, chunks, tail=None):
+        self.comm, self.g, self.tail = comm, g, tail
+        self.chunks = [(int(a), int(b)) for a, b in chunks]
+        tiles = _union(self.chunks)
+        assert len(tiles) == 1 and tiles[0][1] - tiles[0][0] == sum(b - a for a, b in self.chunks), \
+            "FixedScheduleReducer: chunks must tile one range exactly once"
+        self.lo, self.hi = tiles[0]
+        self.final, self.next, self.handles, self.log = [], 0, [], []
+
+    def begin(self, dead_ranges=()):
+        assert not self.handles, "FixedScheduleReducer: begin() before the last schedule's finish()"
+        self.final, self.next, self.log = _union(dead_ranges), 0, []
+        self._advance()
+
+    def _is_final(self, a, b):
+        return any(x <= a and b <= y for x, y in self.final)
+
+    def _send(self, i):
+        a, b = self.chunks[i]
+        self.handles.append(self.comm.all_reduce_async(self.g[a:b]))
+        self.log.append((a, b))
+
+    def _advance(self):
+        while self.next < len(self.chunks) and self._is_final(*self.chunks[self.next]):
+            self._send(self.next)
+            self.next += 1
+
+    def ready(self, a, b):
+        if b <= a:
+            return
+        self.final = _union(self.final + [[a, b]])
+        self._advance()
+
+    def finish(self):
+        while self.next < len(self.chunks):
+            self._send(self.next)
+            self.next += 1
+        if self.tail is not None:
+            self.handles.append(self.comm.all_reduce_async(self.tail))
+            self.log.append(("tail", self.tail.numel()))
+        for h in self.handles:
+            h.wait()
+        self.handles = []

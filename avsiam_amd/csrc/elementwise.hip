@@ -386,6 +386,114 @@ __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__
     }
 }
 
+// The same update once more, as ONE launch over a table of arena segments (data-parallel fine-tuning: which gradient classes take a step is
+// the union over the ranks, known only on the device - include/avsiam_hip.h, avs_adam_table).  Work is cut into chunks of ADT_CHUNK elements:
+// every workgroup builds the exclusive prefix sum of the segments' chunk counts in LDS (the table is a few KB, read from the L2), then walks
+// the chunks blockIdx.x, + gridDim.x, ... and finds each chunk's segment by binary search.  A chunk of a class that is not live is skipped before
+// any of its memory is touched; malformed segments (n <= 0, misaligned or negative lo, group / class out of range) own no chunks.
+struct AdamSeg { long long lo; int n; int group; int cls; };
+struct AdamCtl { float lr[3]; int step[16]; float live[16]; };
+static_assert(sizeof(AdamSeg) == 24 && sizeof(AdamCtl) == 140, "mirrors of avs_adam_seg / avs_adam_ctl (include/avsiam_hip.h)");
+constexpr int ADT_BLOCK = 256, ADT_CHUNK = 4096, ADT_GRID = 2048, ADT_MAX_SEGS = 4096, ADT_NCLS = 16, ADT_NGROUP = 3;
+
+__device__ __forceinline__ int adt_chunks(const AdamSeg& s) {
+    const bool ok = s.n > 0 && (s.n & 3) == 0 && s.lo >= 0 && (s.lo & 3) == 0 && s.group >= 0 && s.group < ADT_NGROUP && s.cls >= 0 && s.cls < ADT_NCLS;
+    return ok ? (s.n - 1) / ADT_CHUNK + 1 : 0;
+}
+
+__global__ __launch_bounds__(ADT_BLOCK) void adam_table_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, bf16_t* __restrict__ pb, const AdamSeg* __restrict__ segs,
+                                                               int n_segs, const AdamCtl* __restrict__ ctl, float b1, float b2, float eps, float wd,
+                                                               float gscale) {
+    __shared__ int pre[ADT_MAX_SEGS + 1];
+    __shared__ int part[ADT_BLOCK];
+    __shared__ float s_bc1[ADT_NCLS], s_bc2[ADT_NCLS], s_lr[ADT_NGROUP];
+    __shared__ int s_live[ADT_NCLS];
+    const int tid = threadIdx.x;
+    if (tid < ADT_NCLS) {
+        const bool live = ctl->live[tid] > 0.f;
+        s_live[tid] = live;
+        if (live) {
+            const double t = (double)(ctl->step[tid] + 1);
+            s_bc1[tid] = (float)(1.0 - pow((double)b1, t));
+            s_bc2[tid] = (float)sqrt(1.0 - pow((double)b2, t));
+        }
+    }
+    if (tid < ADT_NGROUP) s_lr[tid] = ctl->lr[tid];
+    const int per = (n_segs + ADT_BLOCK - 1) / ADT_BLOCK;
+    const int s0 = min(tid * per, n_segs), s1 = min(s0 + per, n_segs);
+    int sum = 0;
+    for (int s = s0; s < s1; ++s) sum += adt_chunks(segs[s]);
+    part[tid] = sum;
+    __syncthreads();
+    int base = 0;
+    for (int k = 0; k < tid; ++k) base += part[k];
+    for (int s = s0; s < s1; ++s) {
+        pre[s] = base;
+        base += adt_chunks(segs[s]);
+    }
+    if (tid == ADT_BLOCK - 1) pre[n_segs] = base;         // (its own slice ends the table, or is empty: base is the total)
+    __syncthreads();
+    const int total = pre[n_segs];
+    for (int c = blockIdx.x; c < total; c += gridDim.x) {
+        int lo = 0, hi = n_segs;                           // largest s with pre[s] <= c: pre[s] <= c < pre[s + 1], a segment that owns chunks
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (pre[mid] <= c) lo = mid; else hi = mid;
+        }
+        const AdamSeg sg = segs[lo];
+        if (!s_live[sg.cls]) continue;
+        const int first = (c - pre[lo]) * ADT_CHUNK;       // < sg.n
+        const size_t off = (size_t)sg.lo + (size_t)first;
+        const int n4 = min(ADT_CHUNK, sg.n - first) / 4;
+        const float lr = s_lr[sg.group], bc1 = s_bc1[sg.cls], bc2_sqrt = s_bc2[sg.cls];
+        const float step = lr / bc1;
+        float4* p4 = reinterpret_cast<float4*>(p + off);
+        const float4* g4 = reinterpret_cast<const float4*>(g + off);
+        float4* m4 = reinterpret_cast<float4*>(m + off);
+        float4* v4 = reinterpret_cast<float4*>(v + off);
+        uint2* pb2 = pb ? reinterpret_cast<uint2*>(pb + off) : nullptr;
+        for (int i = tid; i < n4; i += ADT_BLOCK) {
+            float4 pv = p4[i];
+            const float4 gv = g4[i];
+            float4 mv = m4[i];
+            float4 vv = v4[i];
+            float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float gg = gp[k] * gscale + wd * pp[k];
+                mp[k] = b1 * mp[k] + (1.f - b1) * gg;
+                vp[k] = b2 * vp[k] + (1.f - b2) * gg * gg;
+                pp[k] -= step * mp[k] / (sqrtf(vp[k]) / bc2_sqrt + eps);
+            }
+            p4[i] = pv;
+            m4[i] = mv;
+            v4[i] = vv;
+            if (pb2) {
+                uint2 o;
+                o.x = pack_bf2(pv.x, pv.y);
+                o.y = pack_bf2(pv.z, pv.w);
+                pb2[i] = o;
+            }
+        }
+    }
+}
+
+// step[c] += (live[c] > 0): a kernel of its own behind the update, whose workgroups all read step[]
+__global__ void adam_table_advance_kernel(AdamCtl* ctl) {
+    const int c = threadIdx.x;
+    if (c < ADT_NCLS && ctl->live[c] > 0.f) ctl->step[c] += 1;
+}
+
+// the three learning rates travel as kernel arguments: no staging buffer a step still in flight could be reading
+__global__ void adam_table_lr_kernel(AdamCtl* ctl, float lr0, float lr1, float lr2) {
+    if (threadIdx.x == 0) {
+        ctl->lr[0] = lr0;
+        ctl->lr[1] = lr1;
+        ctl->lr[2] = lr2;
+    }
+}
+
 // ===================================================================================================
 static inline int grid_1d(size_t n, int block) {
     size_t g = (n + block - 1) / block;
@@ -887,5 +995,45 @@ extern "C" int avs_adam_dev(float* p, const float* g, float* m, float* v, bf16_t
     AVS_CHECK_ARG(n > 0 && (n % 4) == 0 && step_dev && p && g && m && v, "adam_dev: n must be a positive multiple of 4, step_dev a device pointer");
     adam_dev_kernel<<<grid_1d(n / 4, 256), 256, 0, stream>>>(p, g, m, v, p_bf16, (size_t)n, lr, beta1, beta2, eps, weight_decay, step_dev, grad_scale);
     AVS_LAUNCH_CHECK("adam_dev");
+    return 0;
+}
+
+extern "C" int avs_adam_table_sized(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, const AdamSeg* segs, int n_segs,
+                                    long long n_chunks, AdamCtl* ctl, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                    hipStream_t stream);
+
+extern "C" int avs_adam_table(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, const AdamSeg* segs, int n_segs,
+                              AdamCtl* ctl, float beta1, float beta2, float eps, float weight_decay, float grad_scale, hipStream_t stream) {
+    return avs_adam_table_sized(p, g, m, v, p_bf16, segs, n_segs, ADT_GRID, ctl, beta1, beta2, eps, weight_decay, grad_scale, stream);
+}
+
+// n_chunks: the table's chunk count, which the host knows from when it built the table (the segments themselves live in device memory): the
+// grid is min(n_chunks, ADT_GRID) workgroups, so a table that owns a handful of chunks (a frozen base) does not launch 2048 of them to build
+// the prefix table and leave.  Any value >= 1 is correct - the chunk loop strides by the grid.
+extern "C" int avs_adam_table_sized(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, const AdamSeg* segs, int n_segs,
+                                    long long n_chunks, AdamCtl* ctl, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                    hipStream_t stream) {
+    AVS_CHECK_ARG(p && g && m && v && segs && ctl && n_segs >= 1 && n_segs <= ADT_MAX_SEGS && n_chunks >= 1,
+                  "adam_table: p, g, m, v, segs, ctl must not be NULL, n_segs in 1..%d (got %d), n_chunks >= 1", ADT_MAX_SEGS, n_segs);
+    const int grid = (int)(n_chunks < ADT_GRID ? n_chunks : ADT_GRID);
+    adam_table_kernel<<<grid, ADT_BLOCK, 0, stream>>>(p, g, m, v, p_bf16, segs, n_segs,
+                                                          ctl, beta1, beta2, eps, weight_decay, grad_scale);
+    AVS_LAUNCH_CHECK("adam_table");
+    adam_table_advance_kernel<<<1, 64, 0, stream>>>(ctl);
+    AVS_LAUNCH_CHECK("adam_table (step counts)");
+    return 0;
+}
+
+extern "C" int avs_adam_table_set_lr(AdamCtl* ctl, float lr_base, float lr_head, float lr_mm, hipStream_t stream) {
+    AVS_CHECK_ARG(ctl, "adam_table_set_lr: ctl must not be NULL");
+    adam_table_lr_kernel<<<1, 64, 0, stream>>>(ctl, lr_base, lr_head, lr_mm);
+    AVS_LAUNCH_CHECK("adam_table_set_lr");
+    return 0;
+}
+
+extern "C" int avs_adam_table_geometry(int* grid, int* chunk_elems, int* max_segs) {
+    if (grid) *grid = ADT_GRID;
+    if (chunk_elems) *chunk_elems = ADT_CHUNK;
+    if (max_segs) *max_segs = ADT_MAX_SEGS;
     return 0;
 }

@@ -17,10 +17,12 @@ The encoder kinds a / v / av are built on first use and bump-allocate their acti
 The fused step of traintest_ft_base.train_step runs the `a` / `v` branches of mm_grad on that modality's encoder alone - exactly what the
 reference's autograd computes for loss_fn(out_a, ...) / loss_fn(out_v, ...) (out_a / out_v read nothing of the other modality).
 """
+import math
+
 import torch
 
 from . import ops
-from .arena import ParamArena
+from .arena import ALIGN, ParamArena
 from .config import AVSiamConfig, EngineOptions
 from .engine import F32, I32, LN_EPS_BLOCK, LN_EPS_FINAL, BlockParams, BufferPool, Norm, _dx_in, _ln_bwd, _ln_fwd, _z, make_stack
 from .ft_engine import Encoder, Head
@@ -41,6 +43,8 @@ class TrainHead(Head):
         self.lnws = _z((ops.layernorm_ws(rp, width),), F32, dev)
         self.wf = arena.w(f"{name}.1.weight")              # fp32 master [L, width]
         self.gw, self.gb = arena.gw(f"{name}.1.weight"), arena.gw(f"{name}.1.bias").view(1, label_dim)
+        own = [n for n in arena.names if n.startswith(name + ".") and arena.info[n].live]
+        self.grange = (min(arena.offset[n] for n in own), max(arena.offset[n] + ops.pad_rows(math.prod(arena.info[n].shape), ALIGN) for n in own))
         self.x = None
 
     def forward(self, x, n):
@@ -177,9 +181,11 @@ class FtTrain:
         if self.pool.owner is not enc:
             raise RuntimeError("CAVMAEFT_BASE: another encoder kind ran its forward since this one's - the shared activations are gone")
 
-    def backward(self, token, live, base=True):
+    def backward(self, token, live, base=True, reducer=None):
         """live: output bits whose logits gradient is in the heads' dlog buffers; base: the encoder (final norms, blocks, patch embeddings)
-        needs gradients.  The caller has zeroed the gradient arena (ParamArena.zero_grad_range)."""
+        needs gradients.  The caller has zeroed the gradient arena (ParamArena.zero_grad_range).
+        reducer (comm.FixedScheduleReducer, data parallel): told the heads' and the blocks' gradient ranges as they become final; the final
+        norms and the patch embeddings are left to its finish()."""
         self.check(token)
         st_ = self.state
         st_["done"] = True
@@ -192,6 +198,8 @@ class FtTrain:
             if not live:
                 return
             head.backward(n, enc.dpool)
+            if reducer is not None:
+                reducer.ready(*head.grange)
             if not base:
                 return
             ops.segment_mean_bwd(enc.dpool, enc.seg_start, enc.yf, enc.nseq)
@@ -207,14 +215,20 @@ class FtTrain:
                     enc.dpool[:2 * B].zero_()
                 if live & OUT_A:
                     self.head_a.backward(B, enc.dpool)
+                    if reducer is not None:
+                        reducer.ready(*self.head_a.grange)
                 if live & OUT_V:
                     self.head_v.backward(B, enc.dpool[B:])
+                    if reducer is not None:
+                        reducer.ready(*self.head_v.grange)
             if live & OUT:
                 sm = j["st"]
                 self.head_mm.backward(B, j["dpooled"].view(-1, 2 * D))
+                if reducer is not None:
+                    reducer.ready(*self.head_mm.grange)
                 ops.segment_mean_bwd(j["dpooled"], j["seg"], sm.dx[0], 2 * B)
                 ops.cast_scale(sm.dx[0], sm.dxb[0], sm.rows * D, 1.0)
-                sm.backward()
+                sm.backward(reducer=reducer)
                 dy = sm.dx[0]
                 if not base:
                     return
@@ -230,7 +244,7 @@ class FtTrain:
             for lo, fin, rows, omap in ((0, self.final[:1], ra, maps[0]), (ra, self.final[1:], enc.rows_v, maps[1])):
                 _ln_bwd(dy if omap is not None else dy[lo:], st.out[lo:], enc.fstat[0][lo:], enc.fstat[1][lo:], fin,
                         _dx_in(st, lo), st.lnws, rows, out_map=omap, dx_bf16=st.dxb[0][lo:], dcol=self.blocks[-1].fc2.gb)
-        st.backward(last_fc2_bias_done=True)
+        st.backward(last_fc2_bias_done=True, reducer=reducer)
         if enc.na:
             enc.emb_a.backward(st.dx[0][:enc.rows_a])
         if enc.nv:

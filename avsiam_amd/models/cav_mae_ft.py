@@ -16,9 +16,16 @@ would reach.  One backward per forward, and every ``.grad`` must be cleared (set
 backward: gradient accumulation across backwards is refused with an error.
 ``train_step`` (traintest_ft_base.train_step) is the fused step: forward of the loss's branch only, the HIP loss kernel, the backward and
 the HIP Adam over the reference's three parameter groups, without a host sync.  The bf16 path only (fp8 fine-tuning is refused).
+Data parallel (``set_distributed`` with an active comm; the reference's DistributedDataParallel(find_unused_parameters=True),
+traintest_ft_base.py:91-92): ranks may run different branches in one step, so the gradients are summed in a message schedule fixed by the
+arena layout (comm.FixedScheduleReducer), the union of the ranks' live gradient classes reaches the device as the schedule's last message,
+and ONE avs_adam_table launch over the whole trainable arena steps exactly those classes - rates, step counts and liveness in device
+memory, no host sync.  ``.grad`` stays None after such a step and the autograd path raises.  No run with more than one rank on RCCL exists:
+verified are the arithmetic and the schedule (tests/test_ft_dp_*.py), not the scaling.
 There is no CPU/eager fallback: ``forward`` without a GPU and libavsiam_hip.so raises.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -89,6 +96,10 @@ def live_classes(mode, live):
     return out
 
 
+GROUPS = ("base", "head", "mm")                                        # index = avs_adam_ctl.lr[]
+CLASSES = ("base_a", "base_v", "base_s", "mm", "mlp_head", "mlp_head_a", "mlp_head_mm", "mlp_head_mm_v2")      # index = avs_adam_ctl.step[] / live[]
+
+
 class _FtNode(torch.autograd.Function):
     """One node for a training forward of CAVMAEFT_BASE: forward launches the kernel schedule, backward the hand-written reverse."""
 
@@ -153,6 +164,9 @@ class CAVMAEFT_BASE(nn.Module):
         self._shadow_dirty = True
         self._versions = None
         self._opt = None                                           # HIP Adam state of train_step / adam_step
+        self._world, self._rank, self._comm, self._dp = 1, 0, None, False
+        self._dps = None                                           # data-parallel step state (_dp_state)
+        self._rates = None                                         # (base, head, mm) learning rates of the last Adam step
 
     def __create_fusion__(self):
         """mm_layer_1/2 <- copies of blocks 10 and 11 (:824-826; the fine-tune CLI calls it after loading a pre-trained
@@ -177,6 +191,7 @@ class CAVMAEFT_BASE(nn.Module):
             self._engines.clear()
             self._train_engines.clear()
             self._opt = None
+            self._dps = None
             self._shadow_dirty = True
         return self
 
@@ -276,7 +291,11 @@ class CAVMAEFT_BASE(nn.Module):
                    eps=1e-8, weight_decay=5e-7):
         """One fused fine-tuning step (traintest_ft_base.py:133-175 without the host): the forward of the loss's branch only, the HIP
         classification loss, the backward and the HIP Adam of the reference's three groups.  -> the loss (device tensor [1], no sync).
-        branch (mm_grad only): "mm" (loss on out), "a" (out_a: the audio encoder alone), "v" (out_v: the frame encoder alone)."""
+        branch (mm_grad only): "mm" (loss on out), "a" (out_a: the audio encoder alone), "v" (out_v: the frame encoder alone).
+        Data parallel (set_distributed with an active comm): the loss is this rank's batch mean; the gradients are summed over the ranks in a
+        rank-independent message schedule and divided by the world size inside the one-launch Adam, which steps every gradient class that ANY
+        rank reached (DistributedDataParallel(find_unused_parameters=True)); ``.grad`` is left None after such a step, and the step counts
+        live on the device (optimizer_steps())."""
         from .. import ops
         from ..ft_train import OUT, OUT_A, OUT_V
         if ftmode not in TRAIN_MODES:
@@ -308,6 +327,9 @@ class CAVMAEFT_BASE(nn.Module):
             eng.loss_buf = (torch.zeros(max(n, B * T), dtype=torch.float32, device=x.device), torch.zeros(1, dtype=torch.float32, device=x.device))
         rows, out = eng.loss_buf
         ops.cls_loss(x, y, n, self.label_dim, ops.CLS_BCE if loss == "BCE" else ops.CLS_CE, rows, out, dx=head.dlog)
+        if self._dp:
+            self._dp_step(eng, cls_mode if mode != "mm_grad" else "mm_grad", bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay)
+            return out.clone()
         names = self._backward(eng, eng.token, cls_mode if mode != "mm_grad" else "mm_grad", bit if mode == "mm_grad" else (OUT_A if cls_mode == "audioonly" else OUT_V))
         self.adam_step(lr, head_lr, mm_lr, names, beta1, beta2, eps, weight_decay)
         return out.clone()
@@ -331,6 +353,7 @@ class CAVMAEFT_BASE(nn.Module):
         for c in classes:
             st["step"][c] = st["step"].get(c, 0) + 1
         mult = {"base": 1.0, "head": head_lr, "mm": mm_lr}
+        self._rates = (lr, lr * head_lr, lr * mm_lr)
         spans = sorted((a.offset[n], a.offset[n] + _padded(a.info[n]),
                         lr * mult[param_group(n)], st["step"][grad_class(n)]) for n in names)
         runs = []
@@ -348,6 +371,158 @@ class CAVMAEFT_BASE(nn.Module):
         if a.with_grads:
             self._versions = sum(p._version for p in self._params.values())
 
+    # ---- data-parallel fine-tuning ------------------------------------------------------------------------------
+    def set_distributed(self, world, rank, comm=None):
+        """comm: the collectives to use (comm.TorchDistComm = RCCL by default; tests inject their own).  With an inactive comm (world 1 and
+        not forced on) nothing changes: train_step, adam_step and the autograd path run what they run without this call.
+        Unlike DistributedDataParallel's constructor this does NOT broadcast rank 0's weights: the ranks must hold identical weights when
+        they call it (the same init seed, or the same --pretrain_path) - from then on the step keeps them identical byte for byte.
+        Step counts of data-parallel steps already taken move back to the host, so a second call (another comm) or a return to the
+        single-process adam_step continues from them."""
+        from ..comm import default_comm
+        self._world, self._rank = world, rank
+        self._comm = comm if comm is not None else default_comm(world)
+        assert self._comm.world == world and self._comm.rank == rank, "comm does not match (world, rank)"
+        self._dp = getattr(self._comm, "active", world > 1)
+        self._drop_dp_state()
+        # the gradient all-reduce overlaps the backward: RCCL's kernels need compute units WHILE a persistent GEMM holds the chip
+        # (CAVMAE_BASE.set_distributed; the knob is process-wide, AVSIAM_CU_RESERVE overrides)
+        if self.arena.p.is_cuda and _lib.env_value("AVSIAM_CU_RESERVE") is None:
+            overlap = os.environ.get("AVSIAM_DP_OVERLAP", "1") != "0"
+            _lib.tuning_set("cu_reserve", 8 if (self._dp and overlap) else 0)
+
+    def _drop_dp_state(self):
+        """forget the device state of the data-parallel step, keeping its step counts: the host dictionary is not maintained while ctl.step
+        counts on the device, and _dp_state() / adam_step start from that dictionary"""
+        if self._dps is not None and self._opt is not None:
+            self._opt["step"] = self.optimizer_steps()
+        self._dps = None
+
+    def dp_schedule(self):
+        """The ordered [a, b) messages of the data-parallel gradient all-reduce: a function of the arena layout alone, the same on every rank
+        whatever branch runs or is frozen.  Order of the mm branch's backward: heads and fusion blocks, encoder blocks last to first, then what
+        is left (embeddings, final norms)."""
+        from ..comm import _union, fixed_schedule
+        a = self.arena
+        lo0, hi0 = a.range[1]
+        span = lambda names: _union((a.offset[n], a.offset[n] + _padded(a.info[n])) for n in names)
+        live = [n for n in a.names if a.info[n].live]
+        units = span(n for n in live if param_group(n) != "base")
+        for i in reversed(range(self.cfg.depth)):
+            units += span(n for n in live if n.startswith(f"vit_base.blocks.{i}."))
+        return fixed_schedule([tuple(u) for u in units], lo0, hi0)
+
+    def dp_dead_ranges(self, classes):
+        """[a, b) ranges of the trainable gradient range that a backward reaching the gradient classes `classes` never writes: every tensor of
+        another class, and every frozen one.  They hold zeros after the step's zero-fill - final from the start (FixedScheduleReducer.begin)."""
+        from ..comm import _union
+        a = self.arena
+        return [tuple(r) for r in _union((a.offset[n], a.offset[n] + _padded(a.info[n])) for n, p in self._params.items()
+                                         if a.info[n].live and (not p.requires_grad or grad_class(n) not in classes))]
+
+    def _adam_table(self, trainable):
+        """ops.AdamTable over the live tensors among `trainable` (offsets from the start of the trainable range), the runs of equal
+        (group, class) merged; None when there are none"""
+        from .. import ops
+        a = self.arena
+        lo0, hi0 = a.range[1]
+        spans = sorted((a.offset[n] - lo0, _padded(a.info[n]), GROUPS.index(param_group(n)), CLASSES.index(grad_class(n)))
+                       for n in trainable if a.info[n].live)
+        segs = []
+        for lo, n, grp, cls in spans:
+            if segs and segs[-1][0] + segs[-1][1] == lo and segs[-1][2:] == [grp, cls]:
+                segs[-1][1] += n
+            else:
+                segs.append([lo, n, grp, cls])
+        return ops.AdamTable(segs, len(CLASSES), hi0 - lo0, a.p.device) if segs else None
+
+    def _dp_state(self):
+        """Device state of the data-parallel step: avs_adam_ctl, the moments, the reducer, and - rebuilt when the trainable set changes - the
+        segment table (runs of equal (group, class) merged; frozen tensors are in no segment)."""
+        from .. import ops
+        from ..comm import FixedScheduleReducer, _union
+        a = self.arena
+        dev = a.p.device
+        lo0, hi0 = a.range[1]
+        st = self._dps
+        if st is None:
+            if self._opt is None:
+                self._opt = {"m": torch.zeros(hi0 - lo0, device=dev), "v": torch.zeros(hi0 - lo0, device=dev), "step": {}}
+            ctl = ops.AdamCtl(dev)
+            if self._opt["step"]:                                  # steps taken before set_distributed: the counts move to the device
+                ctl.step.copy_(torch.tensor([self._opt["step"].get(c, 0) for c in CLASSES] + [0] * (ops.ADAM_TABLE_NCLS - len(CLASSES)),
+                                            dtype=torch.int32))
+            st = self._dps = {"ctl": ctl, "trainable": None, "reducer": FixedScheduleReducer(self._comm, a.g, self.dp_schedule(), tail=ctl.live),
+                              "dead": {}, "livevec": {}}
+        trainable = tuple(self._trainable())
+        if st["trainable"] != trainable:
+            st["table"] = self._adam_table(trainable)
+            st["trainable"], st["dead"] = trainable, {}
+        return st
+
+    def _dp_step(self, eng, cls_mode, bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay):
+        """Backward with the fixed-schedule all-reduce, liveness as its last message, and the one-launch Adam.  No host synchronisation."""
+        from .. import ops
+        from ..comm import _union
+        a = self.arena
+        lo0, hi0 = a.range[1]
+        st = self._dp_state()
+        ctl, red = st["ctl"], st["reducer"]
+        reach = live_classes(cls_mode, bit)
+        names = [n for n in st["trainable"] if grad_class(n) in reach and a.info[n].live]
+        cls = frozenset(grad_class(n) for n in names)
+        base = any(param_group(n) == "base" for n in names)
+        if cls not in st["dead"]:
+            # what this rank's backward never writes: every tensor outside the classes it reaches, and the frozen ones
+            st["dead"][cls] = self.dp_dead_ranges(cls)
+        if cls not in st["livevec"]:
+            st["livevec"][cls] = torch.tensor([1.0 if c in cls else 0.0 for c in CLASSES] + [0.0] * (ops.ADAM_TABLE_NCLS - len(CLASSES)),
+                                              dtype=torch.float32).to(a.p.device)
+        ops.timed("torch_zero_grads", lambda: a.zero_grad_range(1))          # the WHOLE range: other ranks' classes arrive in it
+        red.begin(st["dead"][cls])
+        eng.backward(eng.token, bit if names else 0, base=base, reducer=red)
+        ctl.live.copy_(st["livevec"][cls])
+        red.finish()
+        self._rates = (lr, lr * head_lr, lr * mm_lr)
+        if st["table"] is not None:
+            ctl.set_lr(*self._rates)
+            m, v = self._opt["m"], self._opt["v"]
+            ops.adam_table(a.p[lo0:hi0], a.g[lo0:hi0], m, v, a.pb[lo0:hi0], st["table"], ctl, beta1, beta2, eps, weight_decay,
+                           grad_scale=1.0 / self._world)
+        a.refresh_shadows(None, cast=False)
+        for e in list(self._engines.values()) + list(self._train_engines.values()):
+            e.refresh_heads()
+        if a.with_grads:
+            self._versions = sum(p._version for p in self._params.values())
+
+    def optimizer_steps(self):
+        """{gradient class: Adam updates it has had}.  Data parallel: copied from the device (synchronises)."""
+        if self._dps is not None:
+            steps = self._dps["ctl"].step.cpu().tolist()
+            return {c: steps[i] for i, c in enumerate(CLASSES) if steps[i]}
+        return dict(self._opt["step"]) if self._opt is not None else {}
+
+    def optimizer_state(self):
+        """The Adam state as plain CPU tensors (synchronises): moments over the trainable range, steps per gradient class (CLASSES order),
+        the three rates of the last step.  None before the first step."""
+        if self._opt is None:
+            return None
+        steps = self.optimizer_steps()
+        return {"m": self._opt["m"].detach().cpu(), "v": self._opt["v"].detach().cpu(),
+                "step": torch.tensor([steps.get(c, 0) for c in CLASSES], dtype=torch.int64),
+                "lr": torch.tensor(self._rates if self._rates is not None else (0.0, 0.0, 0.0), dtype=torch.float64)}
+
+    def load_optimizer_state(self, state):
+        lo0, hi0 = self.arena.range[1]
+        if state["m"].numel() != hi0 - lo0 or state["v"].numel() != hi0 - lo0 or state["step"].numel() != len(CLASSES):
+            raise ValueError("load_optimizer_state: the state does not fit this model's trainable range / gradient classes")
+        dev = self.arena.p.device
+        steps = [int(x) for x in state["step"].tolist()]
+        self._opt = {"m": state["m"].to(dev, torch.float32).clone(), "v": state["v"].to(dev, torch.float32).clone(),
+                     "step": {c: k for c, k in zip(CLASSES, steps) if k}}
+        self._rates = tuple(float(x) for x in state["lr"].tolist())
+        self._dps = None                                           # (rebuilt from _opt at the next data-parallel step)
+
     def forward(self, a, v, mode, is_eval=False):
         """a: [B, 1024, 128] fbank; v: [B, T, 3, 224, 224] frames (either may be None when the mode ignores it).
         Returns what the reference returns for the mode; any other mode returns None as there (no else branch)."""
@@ -360,6 +535,9 @@ class CAVMAEFT_BASE(nn.Module):
         if torch.is_grad_enabled() and mode in TRAIN_MODES and not is_eval:        # every is_eval form stays inference-only
             trainable = self._trainable()
             if trainable:
+                if self._dp:
+                    raise RuntimeError("CAVMAEFT_BASE: the autograd path (forward + loss.backward()) is not synchronised between ranks; with "
+                                       "set_distributed active, train with train_step (or evaluate under torch.no_grad() / is_eval=True)")
                 a, v, B, T = self._prepare(a, v, mode)
                 eng = self._train_engine(B, T)
                 self._sync_shadows()

@@ -938,6 +938,77 @@ def adam(p, g, m, v, p_bf16, n, lr, step, beta1=0.95, beta2=0.999, eps=1e-8, wei
               float(grad_scale), _stream())
 
 
+ADAM_TABLE_NCLS, ADAM_TABLE_NGROUP = 16, 3
+
+
+def adam_table_geometry():
+    """(workgroups, elements per chunk, largest n_segs) of avs_adam_table's update kernel"""
+    grid, chunk, segs = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _lib.load().avs_adam_table_geometry(ctypes.byref(grid), ctypes.byref(chunk), ctypes.byref(segs))
+    return grid.value, chunk.value, segs.value
+
+
+class AdamCtl:
+    """avs_adam_ctl on the device, {float lr[3]; int step[16]; float live[16]}: ONE 35-word buffer with typed views.  `live` is a contiguous
+    fp32 view an all-reduce can sum in place."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(3 + 2 * ADAM_TABLE_NCLS, dtype=F32, device=device)
+        self.lr = self.buf[:3]
+        self.step = self.buf[3:3 + ADAM_TABLE_NCLS].view(I32)
+        self.live = self.buf[3 + ADAM_TABLE_NCLS:]
+
+    def set_lr(self, lr_base, lr_head, lr_mm):
+        """the three rates by value, through a one-thread kernel on the current stream (no staging buffer to race with a step in flight)"""
+        _call("avs_adam_table_set_lr", self.buf, float(lr_base), float(lr_head), float(lr_mm), _stream())
+
+
+class AdamTable:
+    """avs_adam_seg[] on the device, validated on the host when it is built: segs = [(lo, n, group, cls), ...] with lo, n multiples of 4,
+    n > 0, 0 <= lo, lo + n <= limit, group 0..2, cls 0..ncls-1 (ncls <= 16), no two segments overlapping."""
+
+    def __init__(self, segs, ncls, limit, device):
+        import numpy as np
+        segs = [tuple(int(x) for x in s) for s in segs]
+        _, chunk, max_segs = adam_table_geometry()
+        if not 1 <= ncls <= ADAM_TABLE_NCLS:
+            raise _lib.AvsiamHipError(f"adam_table: ncls {ncls} out of range (1..{ADAM_TABLE_NCLS})")
+        if not 1 <= len(segs) <= max_segs:
+            raise _lib.AvsiamHipError(f"adam_table: {len(segs)} segments (1..{max_segs})")
+        end = 0
+        for lo, n, grp, cls in sorted(segs):
+            if n <= 0 or n % 4 or lo % 4 or lo < end or lo + n > limit or n >= 1 << 31:
+                raise _lib.AvsiamHipError(f"adam_table: segment [{lo}, {lo + n}) is empty, misaligned, overlaps its neighbour or leaves the arena ({limit})")
+            if not 0 <= grp < ADAM_TABLE_NGROUP or not 0 <= cls < ncls:
+                raise _lib.AvsiamHipError(f"adam_table: segment [{lo}, {lo + n}): group {grp} / class {cls} out of range")
+            end = lo + n
+        host = np.zeros(len(segs), dtype=np.dtype([("lo", "<i8"), ("n", "<i4"), ("group", "<i4"), ("cls", "<i4"), ("pad", "<i4")]))
+        for i, s in enumerate(segs):
+            host[i] = s + (0,)
+        self.segs, self.ncls, self.limit = segs, ncls, limit
+        self.chunks = sum((n + chunk - 1) // chunk for _, n, _, _ in segs)            # sizes the grid (avs_adam_table_sized)
+        self.dev = torch.from_numpy(host.view(np.uint8).copy()).to(device)
+
+
+def adam_table(p, g, m, v, p_bf16, table: AdamTable, ctl: AdamCtl, beta1=0.95, beta2=0.999, eps=1e-8, weight_decay=5e-7, grad_scale=1.0,
+               sized=True):
+    """Adam over every segment of `table` whose class is live in `ctl`, one launch; then ctl.step += (ctl.live > 0).  p, g, m, v (and p_bf16)
+    share the table's element offsets and hold at least table.limit elements.  sized=False: the full grid of avs_adam_table instead of one
+    bounded by the table's chunk count (the same bytes)."""
+    for t in (p, g, m, v):
+        _chk(t, F32, "adam_table")
+    _chk(p_bf16, BF16, "adam_table.p_bf16")
+    _chk(table.dev, U8, "adam_table.segs"); _chk(ctl.buf, F32, "adam_table.ctl")
+    assert all(t.numel() >= table.limit for t in (p, g, m, v)) and (p_bf16 is None or p_bf16.numel() >= table.limit)
+    assert all(t.data_ptr() % 16 == 0 for t in (p, g, m, v)) and (p_bf16 is None or p_bf16.data_ptr() % 8 == 0)
+    if not sized:
+        _call("avs_adam_table", p, g, m, v, p_bf16, table.dev, len(table.segs), ctl.buf, float(beta1), float(beta2), float(eps),
+              float(weight_decay), float(grad_scale), _stream())
+        return
+    _call("avs_adam_table_sized", p, g, m, v, p_bf16, table.dev, len(table.segs), table.chunks, ctl.buf, float(beta1), float(beta2), float(eps),
+          float(weight_decay), float(grad_scale), _stream())
+
+
 # ---- retrieval evaluation -------------------------------------------------------------------------------------------------------------
 RETRIEVAL_MAX_TOPK = 16
 _retr_ws = {}            # (device, stream) -> cached workspace: calls on different streams never share one; grown when a call needs more, so no

@@ -7,11 +7,20 @@ Data flags behave as in the pre-training entry point: --data_train '' or 'synthe
 label-smoothed multi-hot labels (the json/wav/mp4 pipeline is out of scope on this path).  --pretrain_path loads a CAVMAE_BASE checkpoint
 (with or without the 'module.' prefix) with strict=False (:243-249).  Accepted but not implemented: the augmentation flags (freqm, timem,
 noise, mixup), --wa (weight averaging) and --bal - a warning names each one set to a non-default value; --warmup, distillation weights and
-logging are inert.  Data-parallel runs (world size > 1) are refused.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
+logging are inert.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
 Extensions: --steps-per-epoch / --val-steps (synthetic epoch lengths); --device-metrics: the validation metrics come from the HIP counting
 kernel and the [N, C] outputs never leave the device (traintest_ft_base.calculate_stats_device; AP then groups tied scores as sklearn does);
 --eval-frames: after training, the reference launcher's multi-frame protocol (:326-369) on the validation clips - the metric of every frame and
 of the mean over the frames, written to exp_dir/mul_frame_res.csv (needs the mm_grad test mode).
+
+Data parallel: launch through torchrun, one process per GPU, as the reference's recipes do (VGGSound: 8 ranks).  RANK / WORLD_SIZE /
+LOCAL_RANK form the process group (utils.init_distributed_mode), the model gets its collectives (CAVMAEFT_BASE.set_distributed: RCCL) and
+`random` is seeded 87 + local rank, so every rank draws its own mm_grad branch per step as in the reference; each rank trains on its own
+synthetic shard, rank 0 writes the artefacts.  --world_size N without that environment starts nothing and is refused.  --force-dp: issue
+the collectives at world size 1 too (what one GPU can run of this path).  No run with more than one rank on RCCL exists: what is verified
+is the arithmetic and the message schedule (gloo ranks sharing one GPU), not the scaling.
+--pretrain_path <dir>/best_audio_model.pth also restores <dir>/best_optim_state.pth (Adam moments, per-class steps) when it is there and
+is a fine-tuning state of this model; the pre-training loop's file of the same name (torch.optim.Adam's format) is left alone.
 """
 import argparse
 import ast
@@ -75,6 +84,7 @@ def build_parser():
     p.add_argument('--steps-per-epoch', dest="steps_per_epoch", default=20, type=int, help="synthetic-data epoch length")
     p.add_argument('--val-steps', dest="val_steps", default=2, type=int, help="synthetic validation batches per epoch")
     p.add_argument('--device-metrics', dest="device_metrics", action="store_true", help="validation metrics on the device (exact counting kernel)")
+    p.add_argument('--force-dp', dest="force_dp", action="store_true", help="issue the data-parallel collectives at world size 1 too")
     p.add_argument('--eval-frames', dest="eval_frames", action="store_true",
                    help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
     return p
@@ -91,11 +101,38 @@ def load_pretrained(model, path):
     return miss, unexpected
 
 
+def restore_optimizer_state(model, pretrain_path):
+    """Continue Adam where a fine-tuning run left it: only for <dir>/best_audio_model.pth with a best_optim_state.pth beside it that train()
+    of traintest_ft_base wrote (plain tensors m / v / step / lr fitting this model).  The pre-training loop writes a file of the same name in
+    torch.optim.Adam's {'state', 'param_groups'} format beside ITS checkpoints: that one, and anything else that does not fit, is left alone -
+    a weights-only warm start, said so.  -> True when the state was restored."""
+    import torch
+    if os.path.basename(pretrain_path) != 'best_audio_model.pth':
+        return False
+    opt_path = os.path.join(os.path.dirname(pretrain_path), 'best_optim_state.pth')
+    if not os.path.exists(opt_path):
+        return False
+    state = torch.load(opt_path, map_location='cpu')
+    lo, hi = model.arena.range[1]
+    from .models.cav_mae_ft import CLASSES
+    fits = (isinstance(state, dict) and set(state) >= {"m", "v", "step", "lr"} and all(torch.is_tensor(state[k]) for k in ("m", "v", "step", "lr"))
+            and state["m"].numel() == hi - lo and state["v"].numel() == hi - lo and state["step"].numel() == len(CLASSES)
+            and state["lr"].numel() == 3)
+    if not fits:
+        print('{:s} is not a fine-tuning Adam state of this model (a pre-training run writes a file of that name): weights-only warm start, '
+              'Adam restarts'.format(opt_path))
+        return False
+    model.load_optimizer_state(state)
+    print('restored the Adam state (moments, steps {}) from {:s}'.format(model.optimizer_steps(), opt_path))
+    return True
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    world = int(os.environ.get("WORLD_SIZE", args.world_size))
-    if world > 1:
-        raise SystemExit("data-parallel fine-tuning (DDP over RCCL) is not implemented on this path: run one process")
+    launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
+    if args.world_size > 1 and not launched:
+        raise SystemExit("data-parallel fine-tuning is launched through torchrun, one process per GPU (RANK / WORLD_SIZE / LOCAL_RANK in the "
+                         "environment form the process group): --world_size alone starts no ranks")
     if args.data_train not in ('', 'synthetic') or args.data_val not in ('', 'synthetic'):
         raise SystemExit("only synthetic AudioSet-shaped data is supported on this path (see module docstring)")
     if args.ftmode not in ("audioonly", "videoonly", "mm_grad"):
@@ -106,6 +143,23 @@ def main(argv=None):
              if getattr(args, k) not in (off, 'None')]
     if inert:
         print("WARNING: not implemented on this path, ignored: " + ", ".join(inert) + " - this run trains without them", flush=True)
+    import random
+    import torch
+    from . import utils
+    args.local_rank = int(os.environ.get("LOCAL_RANK", 0))
+    if launched:
+        random.seed(87 + args.local_rank)                                     # the reference's per-rank branch draw (run_cavmae_ft_base.py)
+    utils.init_distributed_mode(args)
+    try:
+        return _run(args)
+    finally:
+        utils.restore_print()
+        if args.distributed and torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+
+
+def _run(args):
+    import torch
     from .config import AVSiamConfig
     from .models import CAVMAEFT_BASE
     from .traintest_ft_base import SyntheticFtLoader, evaluate_frames, train
@@ -113,11 +167,20 @@ def main(argv=None):
     model = CAVMAEFT_BASE(label_dim=args.n_class)
     if args.pretrain_path != 'None':
         load_pretrained(model, args.pretrain_path)
-    model = model.cuda()
+    model = model.to(torch.device("cuda", getattr(args, "gpu", 0)))
+    if args.pretrain_path != 'None':
+        restore_optimizer_state(model, args.pretrain_path)
+    if args.world_size > 1 or args.force_dp:
+        from .comm import RcclComm, TorchDistComm
+        if os.environ.get("AVSIAM_COMM", "torch") == "rccl" or not torch.distributed.is_initialized():
+            comm = RcclComm(rank=args.rank, world=args.world_size, always=args.force_dp)
+        else:
+            comm = TorchDistComm(always=args.force_dp)
+        model.set_distributed(args.world_size, args.rank, comm)
     dev = model.arena.p.device
-    train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87, label_smooth=args.label_smooth)
+    train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth)
     val_frames = 10 if (args.ftmode_test or args.ftmode) == "mm_grad" else 1          # validate() runs is_eval=True: mm_grad wants 10 frames
-    val_loader = SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88, label_smooth=args.label_smooth,
+    val_loader = SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank, label_smooth=args.label_smooth,
                                    frames=val_frames)
     os.makedirs(args.exp_dir or ".", exist_ok=True)
     args.exp_dir = args.exp_dir or "."

@@ -4,7 +4,12 @@
 the three parameter groups, no host sync); ``train`` / ``validate`` keep the reference's signatures and returns, branch draw (:133-160), losses
 (:105-110), schedulers (:91-97), freeze_base (:68-71) and artefacts (models/audio_model.{epoch}.pth, best_audio_model.pth, result.csv).
 Deliberate differences: the reference's stray forward outside autocast (:143, which would also break every mode but mm_grad) is not
-reproduced; data-parallel fine-tuning, weight averaging (--wa) and mixup are not implemented.
+reproduced; weight averaging (--wa) and mixup are not implemented.
+Data parallel (the model's set_distributed with an active comm; the reference wraps the model in DistributedDataParallel(
+find_unused_parameters=True), :91-92): every rank draws its own branch and trains on its own shard, the fused step sums the gradients in a
+rank-independent schedule and steps what any rank reached (CAVMAEFT_BASE.train_step); ``validate`` gathers the predictions and targets of
+all ranks (distributed_concat, :22-27); rank 0 alone writes checkpoints, result.csv and the prints.  Verified with gloo ranks sharing one
+GPU and with one rank's collectives forced on; no run with more than one rank on RCCL exists.
 
 Metrics (mAP, mAUC, acc).  ``calculate_stats`` is the host path and the default: numpy on the [N, C] sigmoid outputs copied from the device.
 ``calculate_stats_device`` (``validate`` with ``args.device_metrics``) keeps outputs and targets on the device: the HIP counting kernel
@@ -126,8 +131,11 @@ def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     -> (stats, loss), or (stats, sigmoid outputs, targets) with output_pred - as the reference.
     Differences, deliberate: args.ftmode_test None (the launchers do not pass it; the reference would then select no mode and fail) falls back to
     args.ftmode; a two-dimensional output (videoonly with one frame squeezes its frame axis, :865) gets that axis back before the mean, where
-    the reference would average over the classes; one process only (no distributed_concat).  args.device_metrics (absent: False): the stats
-    come from calculate_stats_device, and no [N, C] tensor is copied to the host."""
+    the reference would average over the classes.  args.device_metrics (absent: False): the stats
+    come from calculate_stats_device, and no [N, C] tensor is copied to the host.
+    Data parallel (the model has an active comm): predictions and targets of all ranks are gathered rank-major and truncated to
+    len(val_sampler.dataset) when a sampler is given (distributed_concat, :22-27); every rank computes the same statistics; the loss stays
+    this rank's own mean, as in the reference."""
     device = audio_model.arena.p.device
     mode = getattr(args, "ftmode_test", None) or args.ftmode
     loss_fn = torch.nn.BCEWithLogitsLoss() if args.loss == "BCE" else torch.nn.CrossEntropyLoss()
@@ -144,6 +152,10 @@ def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     loss = float(torch.stack(losses).mean()) if losses else float("nan")
     audio_output = torch.sigmoid(torch.cat(outs).float())
     target = torch.cat(tgts).float()
+    comm = getattr(audio_model, "_comm", None)
+    if comm is not None and getattr(audio_model, "_dp", False):
+        limit = len(val_sampler.dataset) if val_sampler is not None else None
+        audio_output, target = distributed_concat(comm, audio_output, limit), distributed_concat(comm, target, limit)
     if getattr(args, "device_metrics", False):
         stats = calculate_stats_device(audio_output.mean(dim=1), target)
     else:
@@ -151,6 +163,15 @@ def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     if output_pred:
         return stats, audio_output, target
     return stats, loss
+
+
+def distributed_concat(comm, t, num_total_examples=None):
+    """:22-27 of the reference: every rank's `t` (equal shapes) concatenated rank-major along dim 0, truncated to num_total_examples (the
+    sampler pads the last shard)."""
+    t = t.contiguous()
+    out = torch.empty((comm.world * t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    comm.all_gather(out.view(-1), t.view(-1))
+    return out if num_total_examples is None else out[:num_total_examples]
 
 
 def evaluate_frames(audio_model, loader, args):
@@ -169,8 +190,9 @@ def evaluate_frames(audio_model, loader, args):
     for f, r in enumerate(res[:-1]):
         print(f"{metric} of frame {f} is {r:.4f}", flush=True)
     print(f"multi-frame {metric} is {res[-1]:.4f}", flush=True)
-    os.makedirs(args.exp_dir, exist_ok=True)
-    np.savetxt(os.path.join(args.exp_dir, "mul_frame_res.csv"), res, delimiter=",")
+    if getattr(audio_model, "_rank", 0) == 0:             # (data parallel: every rank holds the gathered predictions, rank 0 writes)
+        os.makedirs(args.exp_dir, exist_ok=True)
+        np.savetxt(os.path.join(args.exp_dir, "mul_frame_res.csv"), res, delimiter=",")
     return res
 
 
@@ -212,10 +234,15 @@ class _LrHolder:
 def train(audio_model, train_loader, test_loader, test_sampler, args):
     """train of the reference (:29-290) with the fused step.  args: ftmode, loss, lr, head_lr, mm_lr, freeze_base, n_epochs, lr_adapt,
     lr_patience, lrscheduler_start / _step / _decay, metrics, exp_dir, save_model, n_print_steps."""
-    if getattr(args, "world_size", 1) > 1:
-        raise SystemExit("data-parallel fine-tuning is not implemented on this path (run one process)")
+    world = getattr(audio_model, "_world", 1)
+    if getattr(args, "world_size", 1) > 1 and world != args.world_size:
+        raise SystemExit(f"data-parallel fine-tuning: args.world_size is {args.world_size} but the model's collectives are set for {world} rank(s) "
+                         "(call model.set_distributed(world, rank) first, as run_cavmae_ft_base.main does under torchrun)")
+    master = getattr(audio_model, "_rank", 0) == 0            # rank 0 alone writes checkpoints, result.csv and the prints
+    say = print if master else (lambda *a, **k: None)
     exp_dir = args.exp_dir
-    os.makedirs(os.path.join(exp_dir, "models"), exist_ok=True)
+    if master:
+        os.makedirs(os.path.join(exp_dir, "models"), exist_ok=True)
     apply_freeze_base(audio_model, bool(getattr(args, "freeze_base", False)))
     mm_lr = args.mm_lr if getattr(args, "mm_lr", None) is not None else args.head_lr
     hold = _LrHolder(args.lr, args.head_lr, mm_lr)
@@ -227,7 +254,7 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
     main_metrics = getattr(args, "metrics", "mAP")
     best_mAP, best_acc, best_epoch = -np.inf, -np.inf, 0
     result = np.zeros([args.n_epochs, 4])
-    global_step = 0
+    global_step, stale = 0, 0
     for epoch in range(1, args.n_epochs + 1):
         t0 = time.time()
         losses = []
@@ -239,24 +266,34 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
                                                  head_lr=head_lr, mm_lr=mm_ratio))
             global_step += 1
             if global_step % args.n_print_steps == 0:
-                print(f"Epoch: [{epoch}][{global_step}] train loss {float(losses[-1]):.5f}", flush=True)
+                say(f"Epoch: [{epoch}][{global_step}] train loss {float(losses[-1]):.5f}", flush=True)
         train_loss = float(torch.stack(losses).mean()) if losses else float("nan")
         stats, valid_loss = validate(audio_model, test_loader, test_sampler, args)
         mAP = float(np.nanmean([s["AP"] for s in stats]))
         mAUC = float(np.nanmean([s["auc"] for s in stats]))
         acc = stats[0]["acc"]
         result[epoch - 1, :] = [acc if main_metrics == "acc" else mAP, mAUC, base_lr, train_loss]
-        np.savetxt(os.path.join(exp_dir, "result.csv"), result, delimiter=",")
-        print(f"epoch {epoch}: mAP {mAP:.6f} mAUC {mAUC:.6f} acc {acc:.6f} train loss {train_loss:.6f} valid loss {valid_loss:.6f} "
+        if master:
+            np.savetxt(os.path.join(exp_dir, "result.csv"), result, delimiter=",")
+        say(f"epoch {epoch}: mAP {mAP:.6f} mAUC {mAUC:.6f} acc {acc:.6f} train loss {train_loss:.6f} valid loss {valid_loss:.6f} "
               f"({time.time() - t0:.1f}s)", flush=True)
         better = mAP > best_mAP if main_metrics == "mAP" else acc > best_acc
+        stale = 0 if mAP > best_mAP else stale + 1
         best_mAP, best_acc = max(best_mAP, mAP), max(best_acc, acc)
-        sd = {"module." + k: t.detach().cpu() for k, t in audio_model.state_dict().items()}
         if better:
             best_epoch = epoch
-            torch.save(sd, os.path.join(exp_dir, "models", "best_audio_model.pth"))
-        if getattr(args, "save_model", False):
-            torch.save(sd, os.path.join(exp_dir, "models", f"audio_model.{epoch}.pth"))
+        if stale == 3:                                     # :229-251: three epochs without a better mAP end the run - here a return, not exit()
+            say(f"early stop at epoch {epoch}: no better mAP for three epochs", flush=True)
+            break
+        if master:
+            sd = {"module." + k: t.detach().cpu() for k, t in audio_model.state_dict().items()}
+            if better:
+                torch.save(sd, os.path.join(exp_dir, "models", "best_audio_model.pth"))
+                opt_state = audio_model.optimizer_state()                   # :256 of the reference: the optimizer beside the best weights
+                if opt_state is not None:
+                    torch.save(opt_state, os.path.join(exp_dir, "models", "best_optim_state.pth"))
+            if getattr(args, "save_model", False):
+                torch.save(sd, os.path.join(exp_dir, "models", f"audio_model.{epoch}.pth"))
         hold.opt.step()                                   # (no gradients: a no-op that keeps the scheduler's step order)
         if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
             scheduler.step(mAP if main_metrics == "mAP" else acc)

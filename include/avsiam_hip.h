@@ -446,6 +446,39 @@ int avs_adam(float* p, const float* g, float* m, float* v, avs_bf16* p_bf16, lon
  * replayed from a captured hipGraph; bias corrections in double as above */
 int avs_adam_dev(float* p, const float* g, float* m, float* v, avs_bf16* p_bf16, long long n, float lr, float beta1,
                  float beta2, float eps, float weight_decay, const int* step_dev, float grad_scale, avs_stream_t stream);
+/* The same update as ONE launch over a table of arena segments, with everything that changes from step to step in device memory - for
+ * data-parallel fine-tuning, where the set of gradient classes that take a step is the union over the ranks and reaches the device as an
+ * all-reduced vector the host never sees.
+ *   segs[n_segs]  device array; lo: element offset from p / g / m / v / p_bf16 (a multiple of 4), n: elements (a positive multiple of 4),
+ *                 group 0..2 selects ctl->lr[], cls 0..15 the step count and liveness.  Segments must not overlap; gaps belong to nobody.
+ *                 A segment that breaks these rules is skipped as a whole.  1 <= n_segs <= 4096.
+ *   ctl           device block: lr[group]; step[c] = updates class c has HAD; live[c] > 0 = class c takes an update now.
+ * For every segment of a live class: t = step[cls] + 1, bias corrections in double, gg = g * grad_scale + weight_decay * p, the bf16 shadow
+ * refreshed when p_bf16 is not NULL - the bytes avs_adam(..., lr[group], step = t, ...) leaves on the same slice.  Segments of classes that
+ * are not live, and the gaps, are not written.  A second, one-workgroup kernel then does step[c] += (live[c] > 0).
+ * NULL p / g / m / v / segs / ctl or n_segs out of range return -2 before any launch.
+ *  avs_adam_table_sized      the same with the table's chunk count (sum over the segments of ceil(n / chunk_elems), known to whoever built the
+ *                            table): the grid is min(n_chunks, the geometry's grid) workgroups instead of the full grid.  n_chunks < 1: -2
+ *  avs_adam_table_set_lr     ctl->lr[] <- the three rates, passed by value (safe while an earlier step is still in flight on the stream)
+ *  avs_adam_table_geometry   launch geometry of the update kernel: workgroups, elements per chunk (a workgroup takes chunk blockIdx,
+ *                            + grid, ...; a table of more than grid * chunk_elems elements sends workgroups round a second time),
+ *                            largest n_segs.  Any pointer may be NULL. */
+typedef struct avs_adam_seg {
+    long long lo;
+    int n, group, cls;
+} avs_adam_seg;
+typedef struct avs_adam_ctl {
+    float lr[3];
+    int step[16];
+    float live[16];
+} avs_adam_ctl;
+int avs_adam_table(float* p, const float* g, float* m, float* v, avs_bf16* p_bf16, const avs_adam_seg* segs, int n_segs,
+                   avs_adam_ctl* ctl, float beta1, float beta2, float eps, float weight_decay, float grad_scale, avs_stream_t stream);
+int avs_adam_table_sized(float* p, const float* g, float* m, float* v, avs_bf16* p_bf16, const avs_adam_seg* segs, int n_segs,
+                         long long n_chunks, avs_adam_ctl* ctl, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                         avs_stream_t stream);
+int avs_adam_table_set_lr(avs_adam_ctl* ctl, float lr_base, float lr_head, float lr_mm, avs_stream_t stream);
+int avs_adam_table_geometry(int* grid, int* chunk_elems, int* max_segs);
 
 /* ---- Collectives of the data-parallel path: thin wrappers over RCCL on a stream of the communicator's own, with event hand-off
  * (SURVEY.md 8(b)).  Replace, on the data path, torch.distributed's all_gather / all_reduce in GatherLayer

@@ -7,6 +7,14 @@ out, a: out_a, v: out_v), the reference's 50 / 25 / 25 mix (traintest_ft_base.py
 number is ms per step (CUDA events over `steps` steps after `warmup`) and samples/s.  kernel_share: one extra profiled mix step per batch
 with every launch timed by HIP events (ops.KernelProfiler): the share of the step in the kernels fine-tuning added (cls_loss,
 segment_mean_bwd_acc) and in layernorm_bwd (all widths; the head-width calls are a handful of them).
+
+    python tools/bench_ft_train.py --adam-table [--out profiles/rNN/ft_adam_table.json]
+the Adam phase of a mm step (update, shadow transposes, head refresh) per batch: one avs_adam launch per contiguous run of the arena
+(adam_step, the single-process path) against the one-launch avs_adam_table, interleaved in one process, three repetitions each.
+
+    python tools/bench_ft_train.py --dp-one-rank [--out profiles/rNN/ft_dp_one_rank.json]
+the whole data-parallel step at ONE rank with the collectives forced on (a one-rank RCCL communicator) beside the plain step of a twin
+model, interleaved, three repetitions.  A scaling number needs more than one GPU and is not produced here.
 """
 import argparse
 import json
@@ -32,12 +40,102 @@ def _time(fn, steps, warmup):
     return e0.elapsed_time(e1) / steps
 
 
+REPS = 3
+
+
+def _spread(xs):
+    return {"ms": [round(x, 4) for x in xs], "mean_ms": round(sum(xs) / len(xs), 4), "spread_ms": round(max(xs) - min(xs), 4)}
+
+
+def _adam_table(args):
+    from avsiam_amd import ops
+    from avsiam_amd.config import AVSiamConfig
+    from avsiam_amd.models import CAVMAEFT_BASE
+    from avsiam_amd.models.cav_mae_ft import CLASSES, grad_class
+    from avsiam_amd.traintest_ft_base import SyntheticFtLoader, apply_freeze_base
+    cfg, L = AVSiamConfig(), 527
+    res = {"metric": "ft_adam_phase", "branch": "mm", "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+           "repetitions": REPS, "geometry": dict(zip(("grid", "chunk_elems", "max_segs"), ops.adam_table_geometry())), "results": {}}
+    for B in [int(b) for b in args.batches.split(",")]:
+        m = CAVMAEFT_BASE(L).cuda()
+        apply_freeze_base(m, False)
+        ld = SyntheticFtLoader(cfg, B, 1, L, m.arena.p.device)
+        m.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch="mm", head_lr=100.0, mm_lr=100.0)       # gradients of a mm step in the arena
+        names = [n for n, p in m._params.items() if p.grad is not None]
+        a = m.arena
+        lo0, hi0 = a.range[1]
+        table, ctl = m._adam_table(tuple(m._trainable())), ops.AdamCtl(a.p.device)
+        live = {grad_class(n) for n in names}
+        ctl.live[:len(CLASSES)] = torch.tensor([1.0 if c in live else 0.0 for c in CLASSES])
+        def runs(i):
+            m.adam_step(1e-4, 100.0, 100.0, names)
+
+        def one(i):
+            ctl.set_lr(1e-4, 1e-2, 1e-2)
+            ops.adam_table(a.p[lo0:hi0], a.g[lo0:hi0], m._opt["m"], m._opt["v"], a.pb[lo0:hi0], table, ctl)
+            a.refresh_shadows(None, cast=False)
+            for e in list(m._engines.values()) + list(m._train_engines.values()):
+                e.refresh_heads()
+
+        t_runs, t_one = [], []
+        for _ in range(REPS):
+            t_runs.append(_time(runs, args.steps, args.warmup))
+            t_one.append(_time(one, args.steps, args.warmup))
+        res["results"][f"batch_{B}"] = {"per_run_launches": _spread(t_runs), "one_launch_table": _spread(t_one), "table_segments": len(table.segs),
+                                        "parameters": int(sum(n for _, n, _, c in table.segs if CLASSES[c] in live))}
+        del m
+        torch.cuda.empty_cache()
+    return res
+
+
+def _dp_one_rank(args):
+    from avsiam_amd import _lib
+    from avsiam_amd.comm import RcclComm
+    from avsiam_amd.config import AVSiamConfig
+    from avsiam_amd.models import CAVMAEFT_BASE
+    from avsiam_amd.traintest_ft_base import SyntheticFtLoader, apply_freeze_base
+    cfg, L = AVSiamConfig(), 527
+    comm = RcclComm(rank=0, world=1, always=True)
+    res = {"metric": "ft_dp_one_rank", "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "repetitions": REPS,
+           "comm": "RcclComm(world=1, always=True)", "note": "cu_reserve is 0 for the plain step and 8 for the data-parallel one, as each runs in production", "results": {}}
+    for B in [int(b) for b in args.batches.split(",")]:
+        plain, dp = CAVMAEFT_BASE(L).cuda(), CAVMAEFT_BASE(L).cuda()
+        for m in (plain, dp):
+            apply_freeze_base(m, False)
+        dp.set_distributed(1, 0, comm)
+        ld = SyntheticFtLoader(cfg, B, 1, L, dp.arena.p.device)
+        r = {}
+        for br in ("mm", "a", "v"):
+            t_p, t_d = [], []
+            for _ in range(REPS):
+                for m, t in ((plain, t_p), (dp, t_d)):
+                    _lib.tuning_set("cu_reserve", 8 if m is dp else 0)
+                    t.append(_time(lambda i, m=m: m.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch=br, head_lr=100.0, mm_lr=100.0),
+                                   args.steps, args.warmup))
+            r[br] = {"plain": _spread(t_p), "dp_one_rank": _spread(t_d)}
+        res["results"][f"batch_{B}"] = r
+        del plain, dp
+        torch.cuda.empty_cache()
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batches", type=str, default="8,64")
+    ap.add_argument("--adam-table", dest="adam_table", action="store_true")
+    ap.add_argument("--dp-one-rank", dest="dp_one_rank", action="store_true")
+    ap.add_argument("--out", type=str, default=None, help="also write the JSON result to this file")
     args = ap.parse_args(argv)
+    if args.adam_table or args.dp_one_rank:
+        res = (_adam_table if args.adam_table else _dp_one_rank)(args)
+        print(json.dumps(res), flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return res
     from avsiam_amd import ops
     from avsiam_amd.config import AVSiamConfig
     from avsiam_amd.models import CAVMAEFT_BASE
