@@ -238,3 +238,61 @@ __device__ __forceinline__ float xf_video(const void* __restrict__ v, const InXf
     if (x.kind == 0) return reinterpret_cast<const float*>(v)[i];
     return ((float)reinterpret_cast<const uint8_t*>(v)[i] * (1.0f / 255.0f) - x.mean[c]) * x.inv_std[c];
 }
+
+// ---- fine-tuning augmentation where the input is read (include/avsiam_hip.h: avs_ft_aug_*; dataloader_ft.py:527-548): SpecAugment masks
+// on the un-normalised fbank, normalisation, then noise and time roll.  Mirrors of the C ABI's plan structs:
+struct AugState { uint32_t key_lo, key_hi; int counter; int pad; };
+struct AugHdr { uint32_t noise_lo, noise_hi; int counter; int n; int pad[4]; };
+struct AugSample { int f0, fn, t0, tn, shift; float amp; int pad[2]; };
+static_assert(sizeof(AugState) == 16 && sizeof(AugHdr) == 32 && sizeof(AugSample) == 32, "mirrors of avs_ft_aug_state / _hdr / _sample");
+
+// launch-constant part of the transform (kernel argument)
+struct AugK {
+    int kind;                        // 0 normalised fp32 | 1 un-normalised fp32 fbank
+    float mean, inv_std, fill;
+};
+
+// one sample's plan record as the element formula wants it: half-open ranges, shift in [0, T).  Per-sample scalars: load ONCE per row / thread
+struct AugRow {
+    int f0, f1, t0, t1, sh;
+    float amp;
+    uint32_t k0, k1;
+};
+
+__device__ __forceinline__ AugRow aug_row(const AugHdr* __restrict__ plan, int b, int T) {
+    AugRow r{0, 0, 0, 0, 0, 0.f, plan->noise_lo, plan->noise_hi};
+    if (b >= 0 && b < plan->n) {                      // (beyond the plan: no augmentation)
+        const AugSample s = reinterpret_cast<const AugSample*>(plan + 1)[b];
+        r.f0 = s.f0; r.f1 = s.f0 + s.fn; r.t0 = s.t0; r.t1 = s.t0 + s.tn;
+        int sh = s.shift % T;
+        r.sh = sh < 0 ? sh + T : sh;
+        r.amp = s.amp;
+    }
+    return r;
+}
+
+// element (sample b, frame t, mel bin f) of the augmented [B, T, F] spectrogram.  Masked cells read nothing.
+__device__ __forceinline__ float aug_audio(const float* __restrict__ a, const AugK& k, const AugRow& r, int b, int t, int f, int T, int F) {
+    int ts = t - r.sh;
+    if (ts < 0) ts += T;
+    float v = k.fill;
+    if (!((ts >= r.t0 && ts < r.t1) || (f >= r.f0 && f < r.f1))) {
+        v = a[((size_t)b * T + ts) * F + f];
+        if (k.kind == 1) v = (v - k.mean) * k.inv_std;
+    }
+    if (r.amp != 0.f) v = fmaf(r.amp, (float)(xf_philox((uint32_t)(ts * F + f), (uint32_t)b, r.k0, r.k1) >> 8) * (1.0f / 16777216.0f), v);
+    return v;
+}
+
+// Philox4x32-10 with all four counter words (xf_philox fixes the upper two at 0), first output word
+__device__ __forceinline__ uint32_t xf_philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}

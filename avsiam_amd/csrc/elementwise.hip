@@ -573,6 +573,120 @@ extern "C" int avs_im2col_video_s(const void* v, const int* row_img, const int* 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Fine-tuning augmentation where the input is read (include/avsiam_hip.h: avs_ft_aug_*; common.h: aug_audio).
+// The audio patch gather of both strides with the element read replaced by the augmented element.  One workgroup per output row, so the
+// sample's plan record is workgroup-uniform: it is loaded once, in front of the element.  Thread (q, p) reads mel bin f * S + p of frame
+// t * S + q - consecutive threads keep reading consecutive mel bins, whatever the roll (it moves whole frames).
+__global__ __launch_bounds__(256) void im2col_audio_aug_kernel(const float* __restrict__ a, const int* __restrict__ row_b, const int* __restrict__ row_tok,
+                                                               bf16_t* __restrict__ out, int rows, int tlen, int mel, int tP, int S,
+                                                               const AugHdr* __restrict__ plan, AugK k) {
+    const int r = blockIdx.x;
+    const int q = threadIdx.x >> 4, p = threadIdx.x & 15;
+    const int b = row_b[r], tok = row_tok[r];
+    const AugRow ar = aug_row(plan, b, tlen);
+    const int f = tok / tP, t = tok - f * tP;
+    const float v = (q < S && p < S) ? aug_audio(a, k, ar, b, t * S + q, f * S + p, tlen, mel) : 0.f;
+    out[(size_t)r * 256 + p * 16 + q] = f2bf(v);
+}
+
+// the two-pass form: out[b, t, :] as the model sees it.  grid (B, ceil(T*F/4 / 256)); F % 4 == 0, so a thread's four elements share a frame
+__global__ __launch_bounds__(256) void augment_audio_kernel(const float* __restrict__ in, float* __restrict__ out, int T, int F,
+                                                            const AugHdr* __restrict__ plan, AugK k) {
+    const int b = blockIdx.x;
+    const int i4 = blockIdx.y * 256 + threadIdx.x;
+    if (i4 >= T * F / 4) return;
+    const AugRow ar = aug_row(plan, b, T);
+    const int t = (i4 * 4) / F, f = (i4 * 4) - t * F;
+    float4 o;
+    o.x = aug_audio(in, k, ar, b, t, f + 0, T, F);
+    o.y = aug_audio(in, k, ar, b, t, f + 1, T, F);
+    o.z = aug_audio(in, k, ar, b, t, f + 2, T, F);
+    o.w = aug_audio(in, k, ar, b, t, f + 3, T, F);
+    *reinterpret_cast<float4*>(out + ((size_t)b * T + t) * F + f) = o;
+}
+
+// The plan of one step, drawn on the device: one thread per sample.  64-bit INTEGER arithmetic on 24-bit uniforms (the header states the
+// formulas), so a host restatement is exact; amp is one exact int -> float conversion, one exact scaling by 2^-24 and one IEEE division.
+__device__ __forceinline__ void aug_span(uint64_t k1, uint64_t k2, int param, int size, int* start, int* n) {
+    const uint64_t value = k1 * (uint64_t)param;                             // u1 * param, 24 fractional bits
+    *n = (int)(value >> 24);
+    *start = (int)((k2 * (((uint64_t)size << 24) - value)) >> 48);           // u2 * (size - value), 48 fractional bits
+}
+
+__global__ __launch_bounds__(256) void ft_aug_draw_kernel(const AugState* __restrict__ state, AugHdr* __restrict__ plan, int B, int T, int F,
+                                                          int freqm, int timem, int noise) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t k0 = state->key_lo, k1 = state->key_hi, c = (uint32_t)state->counter;
+    if (b == 0) {
+        AugHdr h{};
+        h.noise_lo = xf_philox4(c, 0u, 0u, 2u, k0, k1);
+        h.noise_hi = xf_philox4(c, 1u, 0u, 2u, k0, k1);
+        h.counter = (int)c;
+        h.n = B;
+        *plan = h;
+    }
+    if (b >= B) return;
+    uint32_t u[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) u[q] = xf_philox4((uint32_t)b, (uint32_t)q, c, 1u, k0, k1) >> 8;
+    AugSample s{};
+    if (freqm > 0) aug_span(u[0], u[1], freqm, F, &s.f0, &s.fn);
+    if (timem > 0) aug_span(u[2], u[3], timem, T, &s.t0, &s.tn);
+    if (noise) {
+        s.shift = (int)(((uint64_t)u[4] * (uint64_t)(2 * T)) >> 24) - T;
+        s.amp = __fdiv_rn((float)u[5] * (1.0f / 16777216.0f), 10.0f);
+    }
+    reinterpret_cast<AugSample*>(plan + 1)[b] = s;
+}
+
+// counter += 1: a kernel of its own behind the draw, whose workgroups all read the counter
+__global__ void ft_aug_advance_kernel(AugState* state) {
+    if (threadIdx.x == 0) state->counter += 1;
+}
+
+static int avs_make_aug(const AugHdr* plan, int kind, float mean, float std, float fill, AugK* out, const char* who) {
+    if (!plan) { avs_set_error("%s: no augmentation plan", who); return -2; }
+    if (kind != 0 && kind != 1) { avs_set_error("%s: input kind %d (0 normalised fp32 | 1 un-normalised fbank)", who, kind); return -2; }
+    if (kind == 1 && !(std != 0.f)) { avs_set_error("%s: zero std in the input transform", who); return -2; }
+    if (!(fill == fill)) { avs_set_error("%s: the mask fill value is NaN", who); return -2; }
+    AugK k{kind, kind == 1 ? mean : 0.f, kind == 1 ? 1.0f / std : 1.0f, fill};
+    *out = k;
+    return 0;
+}
+
+extern "C" int avs_ft_aug_draw(AugState* state, AugHdr* plan, int B, int T, int F, int freqm, int timem, int noise, hipStream_t stream) {
+    AVS_CHECK_ARG(state && plan && B > 0 && T > 0 && F > 0 && T < 32768 && F < 32768, "ft_aug_draw: bad arguments (state, plan, B > 0, 0 < T, F < 32768)");
+    AVS_CHECK_ARG(freqm >= 0 && freqm <= F && timem >= 0 && timem <= T, "ft_aug_draw: freqm %d / timem %d outside 0..F (%d) / 0..T (%d)", freqm, timem, F, T);
+    ft_aug_draw_kernel<<<ceil_div(B, 256), 256, 0, stream>>>(state, plan, B, T, F, freqm, timem, noise ? 1 : 0);
+    AVS_LAUNCH_CHECK("ft_aug_draw");
+    ft_aug_advance_kernel<<<1, 64, 0, stream>>>(state);
+    AVS_LAUNCH_CHECK("ft_aug_advance");
+    return 0;
+}
+
+extern "C" int avs_im2col_audio_aug(const float* a, const int* row_b, const int* row_tok, bf16_t* out, int rows, int tlen, int mel, int t_patches,
+                                    int stride, const AugHdr* plan, int kind, float mean, float std, float fill, hipStream_t stream) {
+    AVS_CHECK_ARG(rows > 0 && a && row_b && row_tok && out && tlen > 0 && mel > 0 && t_patches > 0 && stride > 0 && stride <= 16,
+                  "im2col_audio_aug: bad args (stride %d)", stride);
+    AugK k;
+    if (int rc = avs_make_aug(plan, kind, mean, std, fill, &k, "im2col_audio_aug")) return rc;
+    im2col_audio_aug_kernel<<<rows, 256, 0, stream>>>(a, row_b, row_tok, out, rows, tlen, mel, t_patches, stride, plan, k);
+    AVS_LAUNCH_CHECK("im2col_audio_aug");
+    return 0;
+}
+
+extern "C" int avs_augment_audio(const float* in, float* out, int B, int T, int F, const AugHdr* plan, int kind, float mean, float std, float fill,
+                                 hipStream_t stream) {
+    AVS_CHECK_ARG(in && out && in != out && B > 0 && T > 0 && F > 0 && (F % 4) == 0, "augment_audio: bad arguments (out of place; F %% 4 == 0)");
+    AugK k;
+    if (int rc = avs_make_aug(plan, kind, mean, std, fill, &k, "augment_audio")) return rc;
+    dim3 grid(B, ceil_div(T * F / 4, 256));
+    augment_audio_kernel<<<grid, 256, 0, stream>>>(in, out, T, F, plan, k);
+    AVS_LAUNCH_CHECK("augment_audio");
+    return 0;
+}
+
 extern "C" int avs_cast_scale_bf16(const float* x, bf16_t* y, long long n, float alpha, hipStream_t stream) {
     AVS_CHECK_ARG(n > 0 && (n % 4) == 0 && x && y, "cast_scale: n must be a positive multiple of 4");
     cast_scale_kernel<<<grid_1d(n / 4, 256), 256, 0, stream>>>(x, y, (size_t)n / 4, alpha);

@@ -750,11 +750,16 @@ class PatchEmbedder:
         self.row_src.copy_(row_src, non_blocking=True)
         self.row_tok.copy_(row_tok, non_blocking=True)
 
-    def forward(self, inp, out, xf=None):
+    def forward(self, inp, out, xf=None, aug=None):
         """inp: audio [B,time,mel] / video [NF,3,H,W] fp32 - or the raw input (un-normalised fbank / uint8 frames) with its
-        transform `xf` (ops.InputXf); out: fp32 [rows(+pad), D] slice of the residual stream."""
+        transform `xf` (ops.InputXf); out: fp32 [rows(+pad), D] slice of the residual stream.
+        aug (ops.FtAug, audio only): the fine-tuning augmentation applied inside the gather.  The gathered rows (self.cols) ARE the augmented
+        patches, and the weight gradient of backward() reads those saved rows: the backward needs nothing of `xf` or `aug`."""
         if self.audio:
-            ops.im2col_audio(inp, self.row_src, self.row_tok, self.cols, self.rows, self.cfg.audio_t, xf, stride=self.cfg.st)
+            if aug is not None:
+                ops.im2col_audio(inp, self.row_src, self.row_tok, self.cols, self.rows, self.cfg.audio_t, xf, stride=self.cfg.st, aug=aug)
+            else:
+                ops.im2col_audio(inp, self.row_src, self.row_tok, self.cols, self.rows, self.cfg.audio_t, xf, stride=self.cfg.st)
         else:
             ops.im2col_video(inp, self.row_src, self.row_tok, self.cols, self.rows, xf, stride=self.cfg.st)
         ops.gemm_nt(self.cols, self.lin.w, out, self.rows, bias=self.lin.b, res=self.pos, res_idx=self.row_tok, alpha=2.0)

@@ -79,12 +79,17 @@ class Encoder:
         self.seg_start = torch.tensor(seg, dtype=I32, device=dev)
         self.pooled = _z((ops.pad_rows(self.nseq, 256), D), F32, dev)
 
-    def forward(self, audio, frames):
+    def forward(self, audio, frames, xf=(None, None), aug=None):
+        """xf: (audio, frames) raw-input transforms (ops.InputXf) or None each; aug: the step's ops.FtAug plan (training forms only).  Both
+        act inside the patch gathers; the saved patch rows are what the embeddings' backward reads, so nothing of them is kept."""
         st = self.stack
         if self.na:
-            self.emb_a.forward(audio, st.x[0][:self.rows_a])
+            if xf[0] is None and aug is None:
+                self.emb_a.forward(audio, st.x[0][:self.rows_a])
+            else:
+                self.emb_a.forward(audio, st.x[0][:self.rows_a], xf[0], aug)
         if self.nv:
-            self.emb_v.forward(frames, st.x[0][self.rows_a:])
+            self.emb_v.forward(frames, st.x[0][self.rows_a:], xf[1])
         st.forward()
         _ln_fwd(st.out, self.final, self.yf, self.fstat[0], self.fstat[1], self.rows, LN_EPS_FINAL, st.row_mod)
 
@@ -122,26 +127,26 @@ class FtForward:
         return self._enc[kind]
 
     # ---- modes ---------------------------------------------------------------------------------------------------
-    def audioonly(self, audio):
+    def audioonly(self, audio, xf=(None, None)):
         enc = self.encoder("a")
-        enc.forward(audio, None)
+        enc.forward(audio, None, xf)
         return self.head_a.forward(enc.pool(), self.B)                                     # [B, L]
 
-    def videoonly(self, frames):
+    def videoonly(self, frames, xf=(None, None)):
         enc = self.encoder("v")
-        enc.forward(None, frames)
+        enc.forward(None, frames, xf)
         return self.head_v.forward(enc.pool(), self.B * self.T).view(self.B, self.T, self.L)
 
-    def retrieval(self, audio, frames, frame_index=5):
+    def retrieval(self, audio, frames, frame_index=5, xf=(None, None)):
         """-> (audio tokens [B, La, D], tokens of frame 5 [B, Lv, D]) after the final norms (:892)."""
         cfg = self.cfg
         enc = self.encoder("av")
-        enc.forward(audio, frames)
+        enc.forward(audio, frames, xf)
         a = enc.yf[:enc.rows_a].view(self.B, cfg.audio_tokens, cfg.embed_dim)
         v = enc.yf[enc.rows_a:enc.rows].view(self.B, self.T, cfg.video_tokens, cfg.embed_dim)
         return a, v[:, frame_index]
 
-    def retrieval_feats(self, audio, frames, out_a, out_v, frame_index=5):
+    def retrieval_feats(self, audio, frames, out_a, out_v, frame_index=5, xf=(None, None)):
         """Clip-level retrieval features (src/retrieval.py:70-78: token mean, then L2 normalisation, of what `retrieval` returns) ->
         out_a / out_v: fp32 [B, D] unit vectors, written in place (slices of the caller's dataset-level buffers: nothing is copied or
         synchronised per batch).  Frames are independent sequences of the encoder (`rearrange(v, 'b t c w h -> (b t) c w h')`,
@@ -158,7 +163,7 @@ class FtForward:
         if enc.frame_index != frame_index:
             enc.emb_v.set_rows((torch.arange(B) * T + frame_index).repeat_interleave(Lv).to(I32), torch.arange(Lv).repeat(B).to(I32))
             enc.frame_index = frame_index
-        enc.forward(audio, frames)
+        enc.forward(audio, frames, xf)
         pooled = enc.pool()
         ops.l2norm_fwd(pooled[:B], out_a, enc.norm[:B])
         ops.l2norm_fwd(pooled[B:2 * B], out_v, enc.norm[B:])
@@ -186,7 +191,7 @@ class FtForward:
             self._joint[nf] = (st, maps_a, map_v, seg_start, pooled)
         return self._joint[nf]
 
-    def mm_grad(self, audio, frames, is_eval):
+    def mm_grad(self, audio, frames, is_eval, xf=(None, None)):
         """is_eval: [B, 10, L] joint logits, one per frame (:961).  Otherwise (out, out_a, out_v) for single-frame clips
         (:1035; the reference's torch.cat of [B,...] audio and [B*T,...] frame tokens only works for T == 1)."""
         B, T = self.B, self.T
@@ -194,7 +199,7 @@ class FtForward:
         if T != nf:
             raise ValueError(f"mm_grad(is_eval={is_eval}) needs clips of {nf} frame(s), got {T} (cav_mae_base.py:940,1022)")
         enc = self.encoder("av")
-        enc.forward(audio, frames)
+        enc.forward(audio, frames, xf)
         st, maps_a, map_v, seg_start, pooled = self._joint_stack(nf)
         xj = st.x[0]
         so = enc.stack.out

@@ -122,8 +122,10 @@ class FtTrain:
         return self._joint
 
     # ---- forward ---------------------------------------------------------------------------------------------
-    def forward(self, mode, audio, frames, heads):
-        """mode: "audioonly" | "videoonly" | "mm_grad" | "mm_a" | "mm_v" (mm_grad's out_a / out_v branch on its modality's encoder alone).
+    def forward(self, mode, audio, frames, heads, xf=(None, None), aug=None):
+        """xf: (audio, frames) raw-input transforms or None each; aug: the step's augmentation plan (ops.FtAug) - both applied inside the
+        patch gathers (ft_engine.Encoder.forward).  The backward is unchanged: the patch embedding's weight gradient reads the saved rows.
+        mode: "audioonly" | "videoonly" | "mm_grad" | "mm_a" | "mm_v" (mm_grad's out_a / out_v branch on its modality's encoder alone).
         heads: live-output bits to compute (OUT, OUT_A, OUT_V; mm_grad only - the single-output modes always compute theirs).
         -> {bit: logits view}"""
         B, T = self.B, self.T
@@ -132,13 +134,13 @@ class FtTrain:
             kind = "a"
             enc = self.encoder(kind)
             self.pool.owner = enc
-            enc.forward(audio, None)
+            enc.forward(audio, None, xf, aug)
             res[OUT_A] = self.head_a.forward(enc.pool(), B)
         elif mode in ("videoonly", "mm_v"):
             kind = "v"
             enc = self.encoder(kind)
             self.pool.owner = enc
-            enc.forward(None, frames)
+            enc.forward(None, frames, xf)
             res[OUT_V] = self.head_v.forward(enc.pool(), B * T)
         elif mode == "mm_grad":
             if T != 1:
@@ -146,7 +148,7 @@ class FtTrain:
             kind = "av"
             enc = self.encoder(kind)
             self.pool.owner = enc
-            enc.forward(audio, frames)
+            enc.forward(audio, frames, xf, aug)
             if heads & OUT:
                 j = self.joint()
                 st, so = j["st"], enc.stack.out

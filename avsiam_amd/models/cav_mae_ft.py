@@ -104,11 +104,11 @@ class _FtNode(torch.autograd.Function):
     """One node for a training forward of CAVMAEFT_BASE: forward launches the kernel schedule, backward the hand-written reverse."""
 
     @staticmethod
-    def forward(ctx, anchor, model, eng, mode, a, v):
+    def forward(ctx, anchor, model, eng, mode, a, v, xf, aug):
         ctx.set_materialize_grads(False)
         from ..ft_train import OUT, OUT_A, OUT_V
         heads = (OUT | OUT_A | OUT_V) if mode == "mm_grad" else 0
-        res = eng.forward(mode, a, v, heads)
+        res = eng.forward(mode, a, v, heads) if xf is None and aug is None else eng.forward(mode, a, v, heads, xf or (None, None), aug)
         ctx.model, ctx.eng, ctx.mode, ctx.token = model, eng, mode, eng.token
         if mode == "audioonly":
             ctx.bits = (OUT_A,)
@@ -133,7 +133,7 @@ class _FtNode(torch.autograd.Function):
             n = g.numel() // eng.L
             h.dlog[:n, :eng.L].copy_(g.reshape(n, eng.L))
         ctx.model._backward(eng, ctx.token, ctx.mode, live)
-        return (None,) * 6
+        return (None,) * 8
 
 
 class CAVMAEFT_BASE(nn.Module):
@@ -167,6 +167,9 @@ class CAVMAEFT_BASE(nn.Module):
         self._world, self._rank, self._comm, self._dp = 1, 0, None, False
         self._dps = None                                           # data-parallel step state (_dp_state)
         self._rates = None                                         # (base, head, mm) learning rates of the last Adam step
+        self._aug_seed = None                                      # set_aug_seed; None: derived from torch's seed at the first draw
+        self._aug_st = None                                        # ops.FtAugState: the augmentation draws' key and counter, on the device
+        self._aug_plans = {}                                       # batch -> the ops.FtAug buffer draw_aug draws into
 
     def __create_fusion__(self):
         """mm_layer_1/2 <- copies of blocks 10 and 11 (:824-826; the fine-tune CLI calls it after loading a pre-trained
@@ -192,6 +195,7 @@ class CAVMAEFT_BASE(nn.Module):
             self._train_engines.clear()
             self._opt = None
             self._dps = None
+            self._aug_st, self._aug_plans = None, {}
             self._shadow_dirty = True
         return self
 
@@ -249,8 +253,51 @@ class CAVMAEFT_BASE(nn.Module):
             if self.arena.with_grads:
                 self._versions = sum(p._version for p in self._params.values())
 
-    def _prepare(self, a, v, mode):
-        """-> (a, v folded to [B*T, C, H, W], B, T) on the model's device, shapes checked"""
+    def _input_xf(self, input_xf, mode):
+        """-> (audio transform | None, frame transform | None) for the inputs `mode` reads, kinds checked; None when input_xf is None"""
+        if input_xf is None:
+            return None
+        from ..ops import InputXf
+        xa, xv = tuple(input_xf)
+        if mode != "videoonly" and not (isinstance(xa, InputXf) and xa.kind == 1):
+            raise ValueError("input_xf = (ops.InputXf.audio(mean, std), ops.InputXf.frames()): the first entry must be an audio transform")
+        if mode != "audioonly" and not (isinstance(xv, InputXf) and xv.kind == 2):
+            raise ValueError("input_xf = (ops.InputXf.audio(mean, std), ops.InputXf.frames()): the second entry must be a frame transform")
+        return (xa if mode != "videoonly" else None, xv if mode != "audioonly" else None)
+
+    # ---- augmentation draws (SpecAugment masks, noise, time roll: ops.FtAug) ---------------------------------------
+    def set_aug_seed(self, seed):
+        """Seed of this model's augmentation draws; the draw counter restarts.  Default (never called): torch.initial_seed() % 2^31 at the
+        first draw, as CAVMAE_BASE derives its plan seed.  The Philox key is (seed, rank): data-parallel ranks augment differently (their
+        weights stay identical byte for byte all the same - that is the reducer's doing, not the inputs')."""
+        self._aug_seed = int(seed)
+        self._aug_st, self._aug_plans = None, {}
+
+    def _aug_state(self):
+        if self._aug_st is None:
+            from ..ops import FtAugState
+            seed = self._aug_seed if self._aug_seed is not None else int(torch.initial_seed() % (2 ** 31))
+            self._aug_st = FtAugState(self.arena.p.device, ((seed & 0xFFFFFFFF) << 32) | (self._rank & 0xFFFFFFFF))
+        return self._aug_st
+
+    def aug_counter(self):
+        """augmentation plans drawn so far (synchronises)"""
+        return self._aug_state().counter()
+
+    def draw_aug(self, batch, freqm=0, timem=0, noise=False, fill=0.0):
+        """The next training step's augmentation plan for `batch` clips, drawn on the device (no host sync) into this model's buffer for that
+        batch size - pass it to the step that follows, before the next draw.  fill: what a masked cell of an already normalised input takes
+        ((0 - dataset_mean) / dataset_std reproduces the reference); raw inputs (input_xf) get that value by themselves."""
+        from ..ops import FtAug
+        st = self._aug_state()
+        plan = FtAug.draw(st, batch, self.cfg.audio_len, self.cfg.n_mels, freqm, timem, noise, out=self._aug_plans.get(batch), fill=fill)
+        plan.fill = float(fill)
+        self._aug_plans[batch] = plan
+        return plan
+
+    def _prepare(self, a, v, mode, xf=None):
+        """-> (a, v folded to [B*T, C, H, W], B, T) on the model's device, shapes checked.  xf (from _input_xf): the inputs are raw - `a` the
+        un-normalised fp32 fbank, `v` uint8 frames, which stay uint8"""
         cfg, dev = self.cfg, self.arena.p.device
         need_a, need_v = mode != "videoonly", mode != "audioonly"
         B = (a if need_a else v).shape[0]
@@ -263,8 +310,22 @@ class CAVMAEFT_BASE(nn.Module):
             if v.dim() != 5 or tuple(v.shape[2:]) != (cfg.in_chans, cfg.img_size, cfg.img_size) or v.shape[0] != B:
                 raise ValueError(f"v must be [B,T,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(v.shape)}")
             T = v.shape[1]
-            v = v.to(dev, torch.float32).contiguous().view(B * T, cfg.in_chans, cfg.img_size, cfg.img_size)
+            if xf is not None:
+                if v.dtype != torch.uint8:
+                    raise ValueError("input_xf for the frames expects uint8 images")
+                v = v.to(dev).contiguous().view(B * T, cfg.in_chans, cfg.img_size, cfg.img_size)
+            else:
+                v = v.to(dev, torch.float32).contiguous().view(B * T, cfg.in_chans, cfg.img_size, cfg.img_size)
         return a, v, B, T
+
+    def _check_aug(self, aug, B, mode):
+        from ..ops import FtAug
+        if not isinstance(aug, FtAug):
+            raise TypeError("aug must be an ops.FtAug plan (model.draw_aug, ops.FtAug.draw / from_arrays)")
+        if mode == "videoonly":
+            raise ValueError("aug augments the audio input; videoonly reads none")
+        if aug.n < B:
+            raise ValueError(f"aug holds {aug.n} sample records for a batch of {B}")
 
     def _backward(self, eng, token, mode, live):
         """Zero the gradient arena, run the reverse of the training forward `token` for the live outputs, deliver .grad.
@@ -288,14 +349,17 @@ class CAVMAEFT_BASE(nn.Module):
         return names
 
     def train_step(self, a, v, labels, lr, ftmode="mm_grad", branch=None, loss="BCE", head_lr=1.0, mm_lr=1.0, beta1=0.95, beta2=0.999,
-                   eps=1e-8, weight_decay=5e-7):
+                   eps=1e-8, weight_decay=5e-7, *, input_xf=None, aug=None):
         """One fused fine-tuning step (traintest_ft_base.py:133-175 without the host): the forward of the loss's branch only, the HIP
         classification loss, the backward and the HIP Adam of the reference's three groups.  -> the loss (device tensor [1], no sync).
         branch (mm_grad only): "mm" (loss on out), "a" (out_a: the audio encoder alone), "v" (out_v: the frame encoder alone).
         Data parallel (set_distributed with an active comm): the loss is this rank's batch mean; the gradients are summed over the ranks in a
         rank-independent message schedule and divided by the world size inside the one-launch Adam, which steps every gradient class that ANY
         rank reached (DistributedDataParallel(find_unused_parameters=True)); ``.grad`` is left None after such a step, and the step counts
-        live on the device (optimizer_steps())."""
+        live on the device (optimizer_steps()).
+        input_xf = (ops.InputXf.audio(mean, std), ops.InputXf.frames()): `a` is the un-normalised fbank and `v` uint8 frames, normalised
+        inside the patch gathers.  aug (ops.FtAug, e.g. draw_aug()): the step's SpecAugment masks, noise and time roll, applied inside the
+        audio patch gather - to the raw fbank with input_xf, to a normalised `a` without; ignored by the branches that read no audio ("v")."""
         from .. import ops
         from ..ft_train import OUT, OUT_A, OUT_V
         if ftmode not in TRAIN_MODES:
@@ -315,10 +379,17 @@ class CAVMAEFT_BASE(nn.Module):
             mode, cls_mode, bit = ftmode, ftmode, (OUT_A if ftmode == "audioonly" else OUT_V)
         for p in self._params.values():                           # the step owns the gradients: optimizer.zero_grad() of :168
             p.grad = None
-        a, v, B, T = self._prepare(a, v, "mm_grad" if mode == "mm_grad" else cls_mode)
+        in_mode = "mm_grad" if mode == "mm_grad" else cls_mode
+        xf = self._input_xf(input_xf, in_mode)
+        a, v, B, T = self._prepare(a, v, in_mode, xf)
+        if aug is not None:
+            if in_mode == "videoonly":
+                aug = None
+            else:
+                self._check_aug(aug, B, in_mode)
         eng = self._train_engine(B, T)
         self._sync_shadows()
-        res = eng.forward(mode, a, v, bit)
+        res = eng.forward(mode, a, v, bit) if xf is None and aug is None else eng.forward(mode, a, v, bit, xf or (None, None), aug)
         head = {OUT: eng.head_mm, OUT_A: eng.head_a, OUT_V: eng.head_v}[bit]
         x = res[bit]
         n = x.shape[0]
@@ -385,6 +456,7 @@ class CAVMAEFT_BASE(nn.Module):
         assert self._comm.world == world and self._comm.rank == rank, "comm does not match (world, rank)"
         self._dp = getattr(self._comm, "active", world > 1)
         self._drop_dp_state()
+        self._aug_st, self._aug_plans = None, {}                   # the rank is part of the augmentation key
         # the gradient all-reduce overlaps the backward: RCCL's kernels need compute units WHILE a persistent GEMM holds the chip
         # (CAVMAE_BASE.set_distributed; the knob is process-wide, AVSIAM_CU_RESERVE overrides)
         if self.arena.p.is_cuda and _lib.env_value("AVSIAM_CU_RESERVE") is None:
@@ -523,9 +595,14 @@ class CAVMAEFT_BASE(nn.Module):
         self._rates = tuple(float(x) for x in state["lr"].tolist())
         self._dps = None                                           # (rebuilt from _opt at the next data-parallel step)
 
-    def forward(self, a, v, mode, is_eval=False):
+    def forward(self, a, v, mode, is_eval=False, *, input_xf=None, aug=None):
         """a: [B, 1024, 128] fbank; v: [B, T, 3, 224, 224] frames (either may be None when the mode ignores it).
-        Returns what the reference returns for the mode; any other mode returns None as there (no else branch)."""
+        Returns what the reference returns for the mode; any other mode returns None as there (no else branch).
+        input_xf (extension, every mode): (ops.InputXf.audio(mean, std), ops.InputXf.frames()) - `a` is then the UN-normalised fbank and
+        `v` uint8 frames as the reference's dataset holds them before its own arithmetic, normalised inside the kernels that read them.
+        aug (extension, the training forms only): an ops.FtAug plan - SpecAugment masks, noise and time roll inside the audio patch gather
+        (dataloader_ft.py:527-548, which the reference applies to the training set alone).  With input_xf=None the masks fall on the
+        normalised `a` (masked cells take aug.fill).  Refused with is_eval=True, in an inference-only mode and on a model without gradients."""
         if mode not in MODES:
             return None
         if not self.arena.p.is_cuda:
@@ -538,37 +615,33 @@ class CAVMAEFT_BASE(nn.Module):
                 if self._dp:
                     raise RuntimeError("CAVMAEFT_BASE: the autograd path (forward + loss.backward()) is not synchronised between ranks; with "
                                        "set_distributed active, train with train_step (or evaluate under torch.no_grad() / is_eval=True)")
-                a, v, B, T = self._prepare(a, v, mode)
+                xf = self._input_xf(input_xf, mode)
+                a, v, B, T = self._prepare(a, v, mode, xf)
+                if aug is not None:
+                    self._check_aug(aug, B, mode)
                 eng = self._train_engine(B, T)
                 self._sync_shadows()
-                return _FtNode.apply(self._params[trainable[0]], self, eng, mode, a, v)
-        cfg, dev = self.cfg, self.arena.p.device
-        need_a, need_v = mode != "videoonly", mode != "audioonly"
-        B = (a if need_a else v).shape[0]
-        T = 1
-        if need_a:
-            if tuple(a.shape[1:]) != (cfg.audio_len, cfg.n_mels):
-                raise ValueError(f"a must be [B,{cfg.audio_len},{cfg.n_mels}], got {tuple(a.shape)}")
-            a = a.to(dev, torch.float32).contiguous()
-        if need_v:
-            if v.dim() != 5 or tuple(v.shape[2:]) != (cfg.in_chans, cfg.img_size, cfg.img_size) or v.shape[0] != B:
-                raise ValueError(f"v must be [B,T,{cfg.in_chans},{cfg.img_size},{cfg.img_size}], got {tuple(v.shape)}")
-            T = v.shape[1]
-            v = v.to(dev, torch.float32).contiguous().view(B * T, cfg.in_chans, cfg.img_size, cfg.img_size)
+                return _FtNode.apply(self._params[trainable[0]], self, eng, mode, a, v, xf, aug)
+        if aug is not None:
+            raise ValueError("aug is a training augmentation (the reference applies it to the training set only): it needs a trainable mode "
+                             f"({', '.join(TRAIN_MODES)}) with is_eval=False, grad mode on and a parameter that requires a gradient")
+        xf = self._input_xf(input_xf, mode)
+        a, v, B, T = self._prepare(a, v, mode, xf)
         eng = self._engine(B, T)
         if self._shadow_dirty or self.arena.with_grads:
             self._sync_shadows()
+        xfa = () if xf is None else (xf,)                          # (no transform: the engine calls of before, argument for argument)
         if mode == "audioonly":
-            out = eng.audioonly(a).clone()
+            out = eng.audioonly(a, *xfa).clone()
             return out.unsqueeze(1) if is_eval else out                                    # :845-847
         if mode == "videoonly":
-            return eng.videoonly(v).clone().squeeze(1)                                     # :865
+            return eng.videoonly(v, *xfa).clone().squeeze(1)                               # :865
         if mode == "retrieval":
             if T <= 5:
                 raise IndexError(f"retrieval returns frame 5 of each clip (cav_mae_base.py:892); got {T} frames")
-            ta, tv = eng.retrieval(a, v)
+            ta, tv = eng.retrieval(a, v, **({} if xf is None else {"xf": xf}))
             return ta.clone(), tv.clone()
-        res = eng.mm_grad(a, v, bool(is_eval))
+        res = eng.mm_grad(a, v, bool(is_eval), *xfa)
         if is_eval:
             return res.clone()
         return tuple(r.clone() for r in res)

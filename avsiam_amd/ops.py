@@ -632,12 +632,122 @@ def _xf_arg(xf, kind, per_sample=None):
     return ctypes.addressof(xf)
 
 
-def im2col_audio(a, row_b, row_tok, out, rows, t_patches, xf=None, stride=16):
-    """stride < 16: patch stride on 16 x 16 patch storage (config.stride) - the S x S corner of every 256-wide row is filled, the rest zero"""
+class FtAugState:
+    """include/avsiam_hip.h: avs_ft_aug_state on the device - {key_lo, key_hi, counter, pad} as ONE int32 [4] buffer.  avs_ft_aug_draw reads
+    the key and the counter and advances the counter; nothing else writes it."""
+
+    def __init__(self, device, key=0, counter=0):
+        key = int(key) & 0xFFFFFFFFFFFFFFFF
+        self.key = key
+        import numpy as np
+        self.buf = torch.from_numpy(np.array([key & 0xFFFFFFFF, key >> 32, int(counter) & 0xFFFFFFFF, 0], dtype=np.uint32).view(np.int32).copy()).to(device)
+
+    def counter(self):
+        """draws so far (synchronises)"""
+        return int(self.buf[2].item())
+
+
+class FtAug:
+    """include/avsiam_hip.h: the augmentation plan of one step on the device - avs_ft_aug_hdr {noise_lo, noise_hi, counter, n, pad[4]} followed
+    by n avs_ft_aug_sample {f0, fn, t0, tn, shift, amp (fp32 bits), pad[2]}: ONE int32 [8 + 8 n] buffer.  ``fill``: what a masked cell of an
+    already NORMALISED input (kind 0) takes; an un-normalised input (kind 1) always takes (0 - mean) * (1 / std), the reference's result."""
+    HDR, REC = 8, 8
+
+    def __init__(self, buf, n, fill=0.0):
+        self.buf, self.n, self.fill = buf, int(n), float(fill)
+
+    @classmethod
+    def draw(cls, state, B, T, F, freqm, timem, noise, out=None, fill=0.0):
+        """draw the next step's plan on the device (no host synchronisation) and advance ``state``.  out: an FtAug of at least B records to
+        draw into (a captured step keeps one buffer); None: a new one."""
+        B, T, F, freqm, timem = int(B), int(T), int(F), int(freqm), int(timem)
+        if not (B > 0 and 0 < T < 32768 and 0 < F < 32768 and 0 <= freqm <= F and 0 <= timem <= T):
+            raise _lib.AvsiamHipError(f"FtAug.draw: B {B}, T {T}, F {F}, freqm {freqm}, timem {timem}: need B > 0, 0 < T, F < 32768, 0 <= freqm <= F, 0 <= timem <= T")
+        _chk(state.buf, I32, "ft_aug.state")
+        if out is None:
+            out = cls(torch.zeros(cls.HDR + cls.REC * B, dtype=I32, device=state.buf.device), B, fill)
+        _chk(out.buf, I32, "ft_aug.plan")
+        if out.buf.numel() < cls.HDR + cls.REC * B or out.buf.device != state.buf.device:
+            raise _lib.AvsiamHipError(f"FtAug.draw: the plan buffer holds {out.buf.numel()} words on {out.buf.device}, {cls.HDR + cls.REC * B} needed on {state.buf.device}")
+        out.n = B
+        _call("avs_ft_aug_draw", state.buf, out.buf, B, T, F, freqm, timem, 1 if noise else 0, _stream())
+        return out
+
+    @classmethod
+    def from_arrays(cls, f0, fn, t0, tn, shift, amp, seed, device="cuda", fill=0.0):
+        """a plan from per-sample host arrays (a loader that draws on the host, tests); seed: the 64-bit Philox key of the noise field"""
+        import numpy as np
+        cols = [np.asarray(x, dtype=np.int64).astype(np.int32).reshape(-1) for x in (f0, fn, t0, tn, shift)]
+        amp = np.asarray(amp, dtype=np.float32).reshape(-1)
+        n = amp.size
+        if n < 1 or any(c.size != n for c in cols):
+            raise _lib.AvsiamHipError("FtAug.from_arrays: f0, fn, t0, tn, shift and amp need one value per sample each")
+        if any((c < 0).any() for c in cols[:4]) or not np.isfinite(amp).all():
+            raise _lib.AvsiamHipError("FtAug.from_arrays: mask starts / lengths must not be negative, amp must be finite")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        host = np.zeros(cls.HDR + cls.REC * n, dtype=np.int32)
+        host[:4] = np.array([seed & 0xFFFFFFFF, seed >> 32, 0, n], dtype=np.uint32).view(np.int32)
+        rec = host[cls.HDR:].reshape(n, cls.REC)
+        for j, c in enumerate(cols):
+            rec[:, j] = c
+        rec[:, 5] = amp.view(np.int32)
+        return cls(torch.from_numpy(host).to(device), n, fill)
+
+    def arrays(self):
+        """the plan back on the host (synchronises): dict of int32 f0, fn, t0, tn, shift, float32 amp, ints noise_key, counter, n"""
+        import numpy as np
+        h = self.buf.cpu().numpy()
+        n = int(h[3])
+        rec = h[self.HDR:self.HDR + self.REC * n].reshape(n, self.REC)
+        u = h[:2].view(np.uint32)
+        out = {k: rec[:, j].copy() for j, k in enumerate(("f0", "fn", "t0", "tn", "shift"))}
+        out.update(amp=rec[:, 5].copy().view(np.float32), noise_key=int(u[0]) | (int(u[1]) << 32), counter=int(h[2]), n=n)
+        return out
+
+
+def _aug_args(aug, xf, kind, mean, std, fill, who):
+    """-> (plan buffer, kind, mean, std, fill) of an augmented read.  From an audio InputXf (kind 1: its mean / std; it must carry no shift /
+    amp of its own - the plan holds the step's) or from explicit kind / mean / std; fill None: the reference's value for the kind."""
+    if not isinstance(aug, FtAug):
+        raise _lib.AvsiamHipError(f"{who}: aug must be an ops.FtAug plan")
+    _chk(aug.buf, I32, f"{who}.plan")
+    if aug.buf.numel() < FtAug.HDR + FtAug.REC * aug.n:
+        raise _lib.AvsiamHipError(f"{who}: the plan buffer is shorter than its {aug.n} records")
+    if xf is not None:
+        if not isinstance(xf, InputXf) or xf.kind != 1:
+            raise _lib.AvsiamHipError("input transform of kind 1 expected")
+        if xf.shift or xf.amp:
+            raise _lib.AvsiamHipError(f"{who}: the input transform carries a shift / amp of its own beside an augmentation plan (the plan holds the step's)")
+        kind, mean, std = 1, xf.mean[0], xf.std[0]
+    kind = int(kind)
+    if fill is None:
+        import numpy as np
+        # (0 - mean) * (1 / std) in fp32, as the kernel normalises
+        fill = float((np.float32(0.0) - np.float32(mean)) * (np.float32(1.0) / np.float32(std))) if kind == 1 and std != 0 else aug.fill
+    return aug.buf, kind, float(mean), float(std), float(fill)
+
+
+def im2col_audio(a, row_b, row_tok, out, rows, t_patches, xf=None, stride=16, aug=None):
+    """stride < 16: patch stride on 16 x 16 patch storage (config.stride) - the S x S corner of every 256-wide row is filled, the rest zero.
+    aug (FtAug): the fine-tuning augmentation applied to every element read; `a` is then the un-normalised fbank when `xf` (an
+    InputXf.audio(mean, std)) is given, the normalised tensor otherwise."""
     _chk(a, F32, "im2col.a", 3); _chk(row_b, I32, "im2col.row_b"); _chk(row_tok, I32, "im2col.row_tok"); _chk(out, BF16, "im2col.out", 2)
     assert out.shape[1] == 256 and out.shape[0] >= rows and row_b.numel() >= rows and row_tok.numel() >= rows
     assert a.shape[1] == t_patches * stride and a.shape[2] % stride == 0
+    if aug is not None:
+        plan, kind, mean, std, fill = _aug_args(aug, xf, 0, 0.0, 1.0, None, "im2col_audio")
+        _call("avs_im2col_audio_aug", a, row_b, row_tok, out, rows, a.shape[1], a.shape[2], t_patches, int(stride), plan, kind, mean, std, fill, _stream())
+        return
     _call("avs_im2col_audio_s", a, row_b, row_tok, out, rows, a.shape[1], a.shape[2], t_patches, int(stride), _xf_arg(xf, 1, a.shape[0]), _stream())
+
+
+def augment_audio(a, out, aug, kind, mean=0.0, std=1.0, fill=None):
+    """the two-pass form of the augmented read: a [B, T, F] fp32 -> out (fp32, same shape, another tensor) as the model sees it"""
+    _chk(a, F32, "augment_audio.in", 3); _chk(out, F32, "augment_audio.out", 3)
+    if tuple(out.shape) != tuple(a.shape) or out.data_ptr() == a.data_ptr() or a.shape[2] % 4 or a.numel() == 0:
+        raise _lib.AvsiamHipError(f"augment_audio: in {tuple(a.shape)} / out {tuple(out.shape)}: same non-empty shape, different tensors, F % 4 == 0")
+    plan, kind, mean, std, fill = _aug_args(aug, None, kind, mean, std, fill, "augment_audio")
+    _call("avs_augment_audio", a, out, a.shape[0], a.shape[1], a.shape[2], plan, kind, mean, std, fill, _stream())
 
 
 def im2col_video(v, row_img, row_tok, out, rows, xf=None, stride=16):

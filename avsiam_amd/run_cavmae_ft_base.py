@@ -5,10 +5,14 @@
 
 Data flags behave as in the pre-training entry point: --data_train '' or 'synthetic' gives AudioSet-shaped synthetic clips with
 label-smoothed multi-hot labels (the json/wav/mp4 pipeline is out of scope on this path).  --pretrain_path loads a CAVMAE_BASE checkpoint
-(with or without the 'module.' prefix) with strict=False (:243-249).  Accepted but not implemented: the augmentation flags (freqm, timem,
-noise, mixup), --wa (weight averaging) and --bal - a warning names each one set to a non-default value; --warmup, distillation weights and
-logging are inert.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
-Extensions: --steps-per-epoch / --val-steps (synthetic epoch lengths); --device-metrics: the validation metrics come from the HIP counting
+(with or without the 'module.' prefix) with strict=False (:243-249).  --freqm / --timem / --noise are the reference's training augmentation
+(dataloader_ft.py:527-548: SpecAugment masks on the un-normalised fbank, normalisation, noise, time roll), drawn per step on the device and
+applied inside the audio patch gather; validation never augments.  Accepted but not implemented: --mixup, --wa (weight averaging) and --bal - a
+warning names each one set to a non-default value (mixup: the reference mixes waveforms before the fbank, frames with a second weight, and
+draws the partner from the whole dataset - not reproducible from a batch of spectrograms); --warmup, distillation weights and logging are
+inert.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
+Extensions: --raw-input (the loaders yield un-normalised fbank and uint8 frames, normalised on the device inside the kernels that read
+them, as in the pre-training launcher); --steps-per-epoch / --val-steps (synthetic epoch lengths); --device-metrics: the validation metrics come from the HIP counting
 kernel and the [N, C] outputs never leave the device (traintest_ft_base.calculate_stats_device; AP then groups tied scores as sklearn does);
 --eval-frames: after training, the reference launcher's multi-frame protocol (:326-369) on the validation clips - the metric of every frame and
 of the mean over the frames, written to exp_dir/mul_frame_res.csv (needs the mm_grad test mode).
@@ -85,6 +89,8 @@ def build_parser():
     p.add_argument('--val-steps', dest="val_steps", default=2, type=int, help="synthetic validation batches per epoch")
     p.add_argument('--device-metrics', dest="device_metrics", action="store_true", help="validation metrics on the device (exact counting kernel)")
     p.add_argument('--force-dp', dest="force_dp", action="store_true", help="issue the data-parallel collectives at world size 1 too")
+    p.add_argument('--raw-input', dest="raw_input", action="store_true",
+                   help="feed un-normalised fbank + uint8 frames and normalise on the device (dataloader_ft.py:534, 461-462)")
     p.add_argument('--eval-frames', dest="eval_frames", action="store_true",
                    help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
     return p
@@ -127,6 +133,22 @@ def restore_optimizer_state(model, pretrain_path):
     return True
 
 
+MIXUP_REASON = ("mixup is not reproducible from a batch of spectrograms: the reference mixes the two WAVEFORMS before the fbank "
+                "(dataloader_ft.py:321-325), mixes the frames with a second, independent weight (:457-458) and draws the partner from the whole "
+                "dataset (:400-417)")
+
+
+def inert_flag_warnings(args):
+    """-> the warning lines for flags this path accepts and ignores (--freqm / --timem / --noise are implemented and not among them)"""
+    inert = [f"--{k} {getattr(args, k)}" for k, off in (("mixup", 0), ("wa", False), ("bal", None)) if getattr(args, k) not in (off, 'None')]
+    out = []
+    if inert:
+        out.append("WARNING: not implemented on this path, ignored: " + ", ".join(inert) + " - this run trains without them")
+    if getattr(args, "mixup", 0) not in (0, 'None'):
+        out.append("WARNING: " + MIXUP_REASON)
+    return out
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -139,10 +161,8 @@ def main(argv=None):
         raise SystemExit(f"--ftmode {args.ftmode}: the trainable modes are audioonly, videoonly and mm_grad")
     if args.eval_frames and (args.ftmode_test or args.ftmode) != "mm_grad":
         raise SystemExit("--eval-frames scores the frames of multi-frame clips: it needs the mm_grad test mode (--ftmode_test mm_grad)")
-    inert = [f"--{k} {getattr(args, k)}" for k, off in (("mixup", 0), ("wa", False), ("freqm", 0), ("timem", 0), ("noise", False), ("bal", None))
-             if getattr(args, k) not in (off, 'None')]
-    if inert:
-        print("WARNING: not implemented on this path, ignored: " + ", ".join(inert) + " - this run trains without them", flush=True)
+    for w in inert_flag_warnings(args):
+        print(w, flush=True)
     import random
     import torch
     from . import utils
@@ -178,10 +198,11 @@ def _run(args):
             comm = TorchDistComm(always=args.force_dp)
         model.set_distributed(args.world_size, args.rank, comm)
     dev = model.arena.p.device
-    train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth)
+    train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
+                                     raw=args.raw_input)
     val_frames = 10 if (args.ftmode_test or args.ftmode) == "mm_grad" else 1          # validate() runs is_eval=True: mm_grad wants 10 frames
     val_loader = SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank, label_smooth=args.label_smooth,
-                                   frames=val_frames)
+                                   frames=val_frames, raw=args.raw_input)
     os.makedirs(args.exp_dir or ".", exist_ok=True)
     args.exp_dir = args.exp_dir or "."
     result = train(model, train_loader, val_loader, None, args)

@@ -5,6 +5,12 @@ the three parameter groups, no host sync); ``train`` / ``validate`` keep the ref
 (:105-110), schedulers (:91-97), freeze_base (:68-71) and artefacts (models/audio_model.{epoch}.pth, best_audio_model.pth, result.csv).
 Deliberate differences: the reference's stray forward outside autocast (:143, which would also break every mode but mm_grad) is not
 reproduced; weight averaging (--wa) and mixup are not implemented.
+Augmentation (dataloader_ft.py:527-548: SpecAugment masks, noise, time roll - training batches only): ``train`` draws one plan per step on the
+device (``model.draw_aug`` from args.freqm / timem / noise) and the step applies it inside the audio patch gather; ``validate`` and
+``evaluate_frames`` never augment and never touch the draw state.  args.raw_input: the loaders yield un-normalised fbank and uint8 frames,
+normalised inside the gathers (args.dataset_mean / dataset_std).  Mixup stays out: the reference mixes waveforms before the fbank
+(dataloader_ft.py:321-325), mixes frames with a second weight (:457-458) and draws the partner from the whole dataset (:400-417) - none of
+that is a function of a [B, T, F] batch of spectrograms.
 Data parallel (the model's set_distributed with an active comm; the reference wraps the model in DistributedDataParallel(
 find_unused_parameters=True), :91-92): every rank draws its own branch and trains on its own shard, the fused step sums the gradients in a
 rank-independent schedule and steps what any rank reached (CAVMAEFT_BASE.train_step); ``validate`` gathers the predictions and targets of
@@ -40,10 +46,19 @@ def draw_branch(prob):
     return "v"
 
 
-def train_step(model, a, v, labels, lr, ftmode, branch=None, loss="BCE", head_lr=50.0, mm_lr=None):
+def train_step(model, a, v, labels, lr, ftmode, branch=None, loss="BCE", head_lr=50.0, mm_lr=None, input_xf=None, aug=None):
     """One fused step; -> the loss (device tensor [1]).  mm_lr None -> head_lr, as the reference's default --mm_lr None would fail
-    (lr * None) and every launcher passes it."""
-    return model.train_step(a, v, labels, lr, ftmode, branch=branch, loss=loss, head_lr=head_lr, mm_lr=head_lr if mm_lr is None else mm_lr)
+    (lr * None) and every launcher passes it.  input_xf / aug: CAVMAEFT_BASE.train_step."""
+    extra = {k: x for k, x in (("input_xf", input_xf), ("aug", aug)) if x is not None}
+    return model.train_step(a, v, labels, lr, ftmode, branch=branch, loss=loss, head_lr=head_lr, mm_lr=head_lr if mm_lr is None else mm_lr, **extra)
+
+
+def input_xf_of(args):
+    """the raw-input transforms of a run (args.raw_input): (InputXf.audio(dataset_mean, dataset_std), InputXf.frames()), else None"""
+    if not getattr(args, "raw_input", False):
+        return None
+    from .ops import InputXf
+    return InputXf.audio(getattr(args, "dataset_mean", -5.081), getattr(args, "dataset_std", 4.4849)), InputXf.frames()
 
 
 def apply_freeze_base(model, freeze):
@@ -140,9 +155,11 @@ def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     mode = getattr(args, "ftmode_test", None) or args.ftmode
     loss_fn = torch.nn.BCEWithLogitsLoss() if args.loss == "BCE" else torch.nn.CrossEntropyLoss()
     outs, tgts, losses = [], [], []
+    xf = input_xf_of(args)
+    extra = {"input_xf": xf} if xf is not None else {}     # never an augmentation: the reference augments the training set only
     with torch.no_grad():
         for a_input, v_input, labels in val_loader:
-            out = audio_model(a_input.to(device), v_input.to(device), mode, is_eval=True)
+            out = audio_model(a_input.to(device), v_input.to(device), mode, is_eval=True, **extra)
             if out.dim() == 2:
                 out = out.unsqueeze(1)
             labels = labels.to(device)
@@ -198,12 +215,18 @@ def evaluate_frames(audio_model, loader, args):
 
 class SyntheticFtLoader:
     """AudioSet-shaped synthetic clips (no dataset here): a ~ N(0,1) [B, target_length, 128], v ~ N(0,1) [B, frames, 3, 224, 224] and
-    label-smoothed multi-hot labels (dataloader.py: 1 - label_smooth on the positives, label_smooth / n_class elsewhere)."""
+    label-smoothed multi-hot labels (dataloader.py: 1 - label_smooth on the positives, label_smooth / n_class elsewhere).
+    raw=True yields what the reference's dataset holds BEFORE its normalisation, as traintest_cavmae_base.SyntheticAVLoader does:
+    un-normalised fbank (AudioSet's mean / std) and uint8 frames, for a consumer that passes input_xf."""
 
-    def __init__(self, cfg, batch_size, steps, n_class, device, seed=87, label_smooth=0.1, frames=1):
+    def __init__(self, cfg, batch_size, steps, n_class, device, seed=87, label_smooth=0.1, frames=1, raw=False):
         import dataclasses
         from .weights import synth_inputs
         a, v = synth_inputs(dataclasses.replace(cfg, frames=frames), batch_size, seed)
+        if raw:
+            a = a * 4.4849 - 5.081
+            v = (v * 0.25 + 0.5).clamp(0, 1).mul(255).round().to(torch.uint8)
+        self.raw = raw
         g = torch.Generator().manual_seed(seed)
         hot = (torch.rand(batch_size, n_class, generator=g) < 0.02).float()
         hot[torch.arange(batch_size), torch.randint(0, n_class, (batch_size,), generator=g)] = 1.0
@@ -233,7 +256,8 @@ class _LrHolder:
 
 def train(audio_model, train_loader, test_loader, test_sampler, args):
     """train of the reference (:29-290) with the fused step.  args: ftmode, loss, lr, head_lr, mm_lr, freeze_base, n_epochs, lr_adapt,
-    lr_patience, lrscheduler_start / _step / _decay, metrics, exp_dir, save_model, n_print_steps."""
+    lr_patience, lrscheduler_start / _step / _decay, metrics, exp_dir, save_model, n_print_steps; optional freqm, timem, noise (the
+    per-step augmentation of the training batches), raw_input with dataset_mean / dataset_std."""
     world = getattr(audio_model, "_world", 1)
     if getattr(args, "world_size", 1) > 1 and world != args.world_size:
         raise SystemExit(f"data-parallel fine-tuning: args.world_size is {args.world_size} but the model's collectives are set for {world} rank(s) "
@@ -255,6 +279,11 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
     best_mAP, best_acc, best_epoch = -np.inf, -np.inf, 0
     result = np.zeros([args.n_epochs, 4])
     global_step, stale = 0, 0
+    xf = input_xf_of(args)
+    freqm, timem, noise = int(getattr(args, "freqm", 0) or 0), int(getattr(args, "timem", 0) or 0), bool(getattr(args, "noise", False))
+    augment = (freqm > 0 or timem > 0 or noise) and args.ftmode != "videoonly"
+    # a masked cell is 0.0 BEFORE the normalisation: raw inputs get that by themselves, a normalised input takes the value by name
+    fill = (0.0 - getattr(args, "dataset_mean", -5.081)) / getattr(args, "dataset_std", 4.4849)
     for epoch in range(1, args.n_epochs + 1):
         t0 = time.time()
         losses = []
@@ -262,8 +291,11 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
         for a_input, v_input, labels in train_loader:
             prob = random.uniform(0, 1)
             branch = draw_branch(prob) if args.ftmode == "mm_grad" else None
+            extra = {"input_xf": xf} if xf is not None else {}
+            if augment:
+                extra["aug"] = audio_model.draw_aug(a_input.shape[0], freqm, timem, noise, fill=fill)
             losses.append(audio_model.train_step(a_input, v_input, labels, base_lr, args.ftmode, branch=branch, loss=args.loss,
-                                                 head_lr=head_lr, mm_lr=mm_ratio))
+                                                 head_lr=head_lr, mm_lr=mm_ratio, **extra))
             global_step += 1
             if global_step % args.n_print_steps == 0:
                 say(f"Epoch: [{epoch}][{global_step}] train loss {float(losses[-1]):.5f}", flush=True)

@@ -368,6 +368,59 @@ int avs_mae_loss_bwd_id(const float* pred, const void* inp, const float* mask, c
                         int L, int C, int H, int W, float nmask, int stride, const avs_input_xf* xf, const int* row_id, int id_base,
                         avs_stream_t stream);
 
+/* ---- fine-tuning augmentation where the input is read (dataloader_ft.py:527-548, training set only, per sample, in this order):
+ * FrequencyMasking(freqm) and TimeMasking(timem) on the un-normalised fbank (mask value 0.0; each skipped when its parameter is 0), then
+ * (fbank - norm_mean) / norm_std, then with `noise`: fbank += rand(T, F) * (rand() / 10) and roll(fbank, randint(-T, T), 0).  Noise lands on
+ * masked cells too and the masks roll with the content, so for output cell (b, t, f), ts = (t - shift_b) mod T:
+ *     value = (ts in [t0_b, t0_b + tn_b) or f in [f0_b, f0_b + fn_b) ? fill : x) + amp_b * U(ts * F + f, b)     (the last step one fma)
+ *     x = (in[b, ts, f] - mean) * (1 / std)   kind 1, un-normalised fp32 fbank (fill is then (0 - mean) * (1 / std) for the reference's result)
+ *     x = in[b, ts, f]                        kind 0, the normalised tensor (no normalisation is applied; fill as the caller says)
+ * U is the Philox4x32-10 stream of avs_normalize_audio / avs_input_xf kind 1 (24-bit uniforms, counter (ts * F + f, b, 0, 0)), keyed by the plan's
+ * noise key: with every mask length 0 the result is avs_input_xf kind 1 with the same shift / amp / seed, bit for bit.  The noise term is skipped
+ * where amp_b == 0.  Mixup is NOT here: the reference mixes waveforms before the fbank (dataloader_ft.py:321-325), frames with a second
+ * weight (:457-458) and draws the partner from the whole dataset (:400-417) - none of it is a function of a [B, T, F] batch.
+ *
+ * The AUGMENTATION PLAN of a step lives in device memory: one avs_ft_aug_hdr followed by hdr.n avs_ft_aug_sample records (32 bytes each).
+ * A sample index at or beyond hdr.n is read as "no augmentation".  shift may be any int (taken mod T); mask ranges are clipped by the
+ * comparisons themselves, so no plan content can make a kernel read out of bounds.
+ *
+ *  avs_ft_aug_draw       draws the plan of the next step on the device from avs_ft_aug_state {key, counter} and then advances the counter by
+ *                        one (a one-thread kernel behind the draw, plain stores).  Everything that changes from step to step is in device
+ *                        memory - the launch arguments are the recipe's constants - so a captured step replays.  Uniforms are the top 24
+ *                        bits k of Philox words, key = the state's, counter words (b, q, state.counter, 1) for quantity q of sample b:
+ *                          q 0, 1 (k1, k2): fn = (k1 * freqm) >> 24;  f0 = (k2 * ((F << 24) - k1 * freqm)) >> 48       [64-bit integers only;
+ *                          q 2, 3 (k1, k2): tn = (k1 * timem) >> 24;  t0 = (k2 * ((T << 24) - k1 * timem)) >> 48        torchaudio's mask_along_axis:
+ *                                                                     value = u1 * param; min = u2 * (size - value); [floor(min), floor(min) + floor(value))]
+ *                          q 4: shift = ((k * 2T) >> 24) - T          q 5: amp = ((float)k / 2^24) / 10.0f  (both 0 unless `noise`)
+ *                        The noise key is (Philox(counter, 0, 0, 2), Philox(counter, 1, 0, 2)) under the same key: counter word 3 keeps the
+ *                        draws (1), the key derivation (2) and the noise field (0) apart.  0 <= freqm <= F, 0 <= timem <= T, T, F < 32768.
+ *  avs_im2col_audio_aug  avs_im2col_audio_s (stride 1..16) with the element read replaced by the formula above
+ *  avs_augment_audio     the two-pass form, [B, T, F] -> fp32 [B, T, F] as the model sees it (out of place, F % 4 == 0): what
+ *                        avs_normalize_audio is to avs_input_xf; the tests compare the fused read with it
+ * Bad arguments (NULL plan, kind other than 0 | 1, std == 0 for kind 1, ...) return -2 before anything is launched. */
+typedef struct avs_ft_aug_state {
+    unsigned key_lo, key_hi;       /* Philox key of every draw */
+    int counter;                   /* draws so far */
+    int pad;
+} avs_ft_aug_state;
+typedef struct avs_ft_aug_hdr {
+    unsigned noise_lo, noise_hi;   /* Philox key of this step's noise field */
+    int counter;                   /* state.counter the plan was drawn at (information) */
+    int n;                         /* sample records that follow */
+    int pad[4];
+} avs_ft_aug_hdr;
+typedef struct avs_ft_aug_sample {
+    int f0, fn, t0, tn;            /* masked mel bins [f0, f0 + fn), masked frames [t0, t0 + tn) of the UN-rolled input */
+    int shift;                     /* time roll */
+    float amp;                     /* noise amplitude */
+    int pad[2];
+} avs_ft_aug_sample;
+int avs_ft_aug_draw(avs_ft_aug_state* state, avs_ft_aug_hdr* plan, int B, int T, int F, int freqm, int timem, int noise, avs_stream_t stream);
+int avs_im2col_audio_aug(const float* a, const int* row_b, const int* row_tok, avs_bf16* out, int rows, int tlen, int mel, int t_patches,
+                         int stride, const avs_ft_aug_hdr* plan, int kind, float mean, float std, float fill, avs_stream_t stream);
+int avs_augment_audio(const float* in, float* out, int B, int T, int F, const avs_ft_aug_hdr* plan, int kind, float mean, float std,
+                      float fill, avs_stream_t stream);
+
 
 /* ---- bidirectional InfoNCE (forward_contrastive, cav_mae_base.py:641-661) */
 int avs_l2norm_fwd(const float* x, float* xn, float* norm, int rows, int D, avs_stream_t stream);

@@ -15,6 +15,14 @@ the Adam phase of a mm step (update, shadow transposes, head refresh) per batch:
     python tools/bench_ft_train.py --dp-one-rank [--out profiles/rNN/ft_dp_one_rank.json]
 the whole data-parallel step at ONE rank with the collectives forced on (a one-rank RCCL communicator) beside the plain step of a twin
 model, interleaved, three repetitions.  A scaling number needs more than one GPU and is not produced here.
+
+    python tools/bench_ft_train.py --aug [--out profiles/rNN/ft_aug_bench.json]
+the mm and a steps three ways, interleaved in one process, three repetitions each: "plain" (no augmentation), "fused" (freqm 48, timem 192,
+noise: one plan draw per step and the augmentation inside the audio patch gather) and "two_pass" (the same draw, preprocess.augment_fbank
+into a second tensor, then the plain step).  All three read a normalised fbank, so the only difference is the augmentation.
+    python tools/bench_ft_train.py --aug --plain-only --tree <checkout of another commit, built> [--label parent]
+the plain step alone with the package of another tree (the parent commit, which has no augmentation to time): run it alternately with the
+line above and compare "plain" with "plain".
 """
 import argparse
 import json
@@ -119,6 +127,44 @@ def _dp_one_rank(args):
     return res
 
 
+def _aug(args):
+    from avsiam_amd.config import AVSiamConfig
+    from avsiam_amd.models import CAVMAEFT_BASE
+    from avsiam_amd.traintest_ft_base import SyntheticFtLoader, apply_freeze_base
+    import avsiam_amd
+    cfg, L = AVSiamConfig(), 527
+    res = {"metric": "ft_aug_step", "label": args.label, "package": os.path.dirname(os.path.abspath(avsiam_amd.__file__)),
+           "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "repetitions": REPS,
+           "recipe": {"freqm": 48, "timem": 192, "noise": True, "ftmode": "mm_grad", "n_class": L}, "results": {}}
+    for B in [int(b) for b in args.batches.split(",")]:
+        m = CAVMAEFT_BASE(L).cuda()
+        apply_freeze_base(m, False)
+        ld = SyntheticFtLoader(cfg, B, 1, L, m.arena.p.device)
+        kw = dict(head_lr=100.0, mm_lr=100.0)
+        r = {}
+        for br in ("mm", "a"):
+            ways = {"plain": lambda i, br=br: m.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch=br, **kw)}
+            if not args.plain_only:
+                from avsiam_amd import preprocess
+
+                def fused(i, br=br):
+                    m.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch=br, aug=m.draw_aug(B, 48, 192, True, fill=1.133), **kw)
+
+                def two_pass(i, br=br):
+                    m.train_step(preprocess.augment_fbank(ld.a, m.draw_aug(B, 48, 192, True, fill=1.133), raw=False), ld.v, ld.y, 1e-4, "mm_grad",
+                                 branch=br, **kw)
+                ways.update(fused=fused, two_pass=two_pass)
+            t = {k: [] for k in ways}
+            for _ in range(REPS):
+                for k, fn in ways.items():
+                    t[k].append(_time(fn, args.steps, args.warmup))
+            r[br] = {k: _spread(x) for k, x in t.items()}
+        res["results"][f"batch_{B}"] = r
+        del m
+        torch.cuda.empty_cache()
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -126,10 +172,18 @@ def main(argv=None):
     ap.add_argument("--batches", type=str, default="8,64")
     ap.add_argument("--adam-table", dest="adam_table", action="store_true")
     ap.add_argument("--dp-one-rank", dest="dp_one_rank", action="store_true")
+    ap.add_argument("--aug", action="store_true", help="the mm / a steps plain, with the fused augmentation and with the two-pass one")
+    ap.add_argument("--plain-only", dest="plain_only", action="store_true", help="with --aug: time the plain step only")
+    ap.add_argument("--tree", type=str, default=None, help="with --aug --plain-only: import avsiam_amd from this checkout")
+    ap.add_argument("--label", type=str, default=None, help="copied into the result")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON result to this file")
     args = ap.parse_args(argv)
-    if args.adam_table or args.dp_one_rank:
-        res = (_adam_table if args.adam_table else _dp_one_rank)(args)
+    if args.tree:
+        if not (args.aug and args.plain_only):
+            ap.error("--tree goes with --aug --plain-only")
+        sys.path.insert(0, os.path.abspath(args.tree))
+    if args.adam_table or args.dp_one_rank or args.aug:
+        res = (_adam_table if args.adam_table else _dp_one_rank if args.dp_one_rank else _aug)(args)
         print(json.dumps(res), flush=True)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
