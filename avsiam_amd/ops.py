@@ -1286,3 +1286,124 @@ def classification_stats(scores, target, ws=None):
         out = {k: v[0] for k, v in out.items()}
     out["packed"] = packed
     return out
+
+
+# ---- waveform input (fine-tuning loader: dataloader_ft.py:277-340, 441-458) -------------------------------------------------------------
+FBANK_FRAME, FBANK_SHIFT, FBANK_NMEL = 400, 160, 128      # csrc/frontend_math.h
+
+
+def _per_clip(x, B, dtype, name, dev, lo=None, hi=None):
+    """a per-clip vector for a kernel: None stays None; a device tensor is taken as it is (its values are the caller's word - nothing here
+    synchronises to read them); host values (sequence, numpy, CPU tensor) are range-checked and uploaded"""
+    if x is None:
+        return None
+    if torch.is_tensor(x) and x.is_cuda:
+        _chk(x, dtype, name, 1)
+        if x.numel() != B or x.device != dev:
+            raise _lib.AvsiamHipError(f"{name}: expected {B} values on {dev}, got {tuple(x.shape)} on {x.device}")
+        return x
+    h = torch.as_tensor(x).reshape(-1)
+    if h.numel() != B:
+        raise _lib.AvsiamHipError(f"{name}: expected {B} values, got {h.numel()}")
+    if lo is not None and B and (int(h.min()) < lo or int(h.max()) > hi):
+        raise ValueError(f"{name}: values must lie in {lo} .. {hi}, got {h.tolist()}")
+    return h.to(dtype).to(dev)
+
+
+def wave_sums(wave, lengths=None, partner=None, partner_lengths=None, out=None):
+    """The three sums per clip the fbank's sample read needs (avs_wave_sums): [B, 3] float64 = sum w1 over its length, sum w2 over its length,
+    sum w2 over min of the two lengths (the last two 0 without a partner).  wave / partner fp32 [B, stride]; lengths / partner_lengths int32
+    device tensors or None (the stride).  One fixed-order reduction per clip: two calls give identical bytes."""
+    _chk(wave, F32, "wave_sums.wave", 2)
+    B = wave.shape[0]
+    _chk(lengths, I32, "wave_sums.lengths", 1); _chk(partner, F32, "wave_sums.partner", 2); _chk(partner_lengths, I32, "wave_sums.partner_lengths", 1)
+    if partner is not None and (partner.shape[0] != B or partner.device != wave.device):
+        raise _lib.AvsiamHipError(f"wave_sums: partner {tuple(partner.shape)} on {partner.device} does not match wave {tuple(wave.shape)} on {wave.device}")
+    for t, name in ((lengths, "lengths"), (partner_lengths, "partner_lengths")):
+        if t is not None and (t.numel() != B or t.device != wave.device):
+            raise _lib.AvsiamHipError(f"wave_sums.{name}: expected {B} values on {wave.device}")
+    if partner is None and partner_lengths is not None:
+        raise _lib.AvsiamHipError("wave_sums: partner_lengths without a partner")
+    if out is None:
+        out = torch.empty((B, 3), dtype=torch.float64, device=wave.device)
+    else:
+        _chk(out, torch.float64, "wave_sums.out", 2)
+        if tuple(out.shape) != (B, 3) or out.device != wave.device:
+            raise _lib.AvsiamHipError(f"wave_sums.out: expected [{B}, 3] on {wave.device}, got {tuple(out.shape)} on {out.device}")
+    _call("avs_wave_sums", wave, wave.shape[1], lengths, partner, partner.shape[1] if partner is not None else 0, partner_lengths, B, out, _stream())
+    return out
+
+
+def kaldi_fbank(wave, lengths=None, *, partner=None, partner_lengths=None, lam=None, target_length=1024, n_mels=128, norm=None, out=None):
+    """Kaldi log-mel filterbank of a batch of waveforms on the device (avs_wave_sums + avs_kaldi_fbank; the specification is
+    preprocess.kaldi_fbank_reference): what torchaudio.compliance.kaldi.fbank(htk_compat=True, sample_frequency=16000, use_energy=False,
+    window_type='hanning', num_mel_bins=128, dither=0.0, frame_shift=10) and the loader around it compute (dataloader_ft.py:277-340).
+
+    wave fp32 [B, stride] (16 kHz); lengths: samples per clip, None = stride.  partner / partner_lengths / lam: waveform mixup (:298-322) -
+    clip b with lam[b] >= 0 becomes lam (w1 - mean) + (1 - lam) (w2 - mean, zero-padded or cut to the clip's length), minus its mean;
+    lam[b] < 0, lam None or partner None: the plain path, w - mean.  The per-clip vectors may be host values (sequences, numpy, CPU
+    tensors: checked here - a clip under 400 samples or beyond the stride is a ValueError - and uploaded) or device tensors (int32 / fp32,
+    taken at their word: a clip under 400 samples then gives pad rows only).  norm=(mean, std): every row becomes
+    (value - mean) * fp32(1 / std), pad rows included.  n_mels must be 128 (512-point FFT at 16 kHz).
+    -> [B, target_length, 128] fp32: rows 0 .. m - 1 the clip's frames (m = 1 + (n - 400) // 160, cut at target_length), the rest 0 (or the
+    normalised 0).  Two launches, no host synchronisation, no atomics: two calls give identical bytes."""
+    _chk(wave, F32, "kaldi_fbank.wave", 2)
+    B, stride = wave.shape
+    dev = wave.device
+    if int(n_mels) != FBANK_NMEL:
+        raise _lib.AvsiamHipError(f"kaldi_fbank: n_mels = {n_mels}: the kernel is built for 128 mel bins over a 512-point FFT at 16 kHz")
+    if B < 1 or stride < FBANK_FRAME:
+        raise ValueError(f"kaldi_fbank: wave {tuple(wave.shape)}: need at least one clip of at least {FBANK_FRAME} samples")
+    target_length = int(target_length)
+    if target_length < 1:
+        raise _lib.AvsiamHipError(f"kaldi_fbank: target_length = {target_length}")
+    _chk(partner, F32, "kaldi_fbank.partner", 2)
+    if partner is None and (partner_lengths is not None or lam is not None):
+        raise _lib.AvsiamHipError("kaldi_fbank: partner_lengths / lam without a partner")
+    if partner is not None and (partner.shape[0] != B or partner.device != dev or partner.shape[1] < 1):
+        raise _lib.AvsiamHipError(f"kaldi_fbank: partner {tuple(partner.shape)} on {partner.device} does not match wave {tuple(wave.shape)} on {dev}")
+    lengths = _per_clip(lengths, B, I32, "kaldi_fbank.lengths", dev, FBANK_FRAME, stride)
+    partner_lengths = _per_clip(partner_lengths, B, I32, "kaldi_fbank.partner_lengths", dev, 1, partner.shape[1] if partner is not None else 0)
+    lam = _per_clip(lam, B, F32, "kaldi_fbank.lam", dev)
+    if out is None:
+        out = torch.empty((B, target_length, FBANK_NMEL), dtype=F32, device=dev)
+    else:
+        _chk(out, F32, "kaldi_fbank.out", 3)
+        if tuple(out.shape) != (B, target_length, FBANK_NMEL) or out.device != dev:
+            raise _lib.AvsiamHipError(f"kaldi_fbank.out: expected {(B, target_length, FBANK_NMEL)} on {dev}, got {tuple(out.shape)} on {out.device}")
+    mean, std = (float(norm[0]), float(norm[1])) if norm is not None else (0.0, 1.0)
+    if std == 0.0:
+        raise _lib.AvsiamHipError("kaldi_fbank: zero std")
+    sums = wave_sums(wave, lengths, partner, partner_lengths)
+    m = min(target_length, 1 + (stride - FBANK_FRAME) // FBANK_SHIFT)
+    _launch("kaldi_fbank", (0.0, 4.0 * B * (m * FBANK_SHIFT * (2 if partner is not None else 1) + target_length * FBANK_NMEL)), "avs_kaldi_fbank", wave, stride,
+            lengths, partner, partner.shape[1] if partner is not None else 0, partner_lengths, lam, sums, B, target_length, FBANK_NMEL, out,
+            1 if norm is not None else 0, mean, std, _stream())
+    return out
+
+
+def mix_frames(v_u8, partner_u8, weight, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), out=None):
+    """The frame side of mixup (dataloader_ft.py:441-458): v_u8, partner_u8 uint8 [B, ..., 3, H, W] -> fp32 weight_b n(v) + (1 - weight_b) n(partner),
+    n(x) = (x / 255 - mean_c) / std_c as preprocess.normalize_frames.  weight: [B] fp32 (device tensor, or host values that are uploaded);
+    weight_b = 1 gives normalize_frames(v_u8)'s bytes.  One launch, no host synchronisation."""
+    _chk(v_u8, U8, "mix_frames.v"); _chk(partner_u8, U8, "mix_frames.partner")
+    if v_u8.dim() < 4 or v_u8.shape[-3] != 3 or v_u8.shape != partner_u8.shape or v_u8.device != partner_u8.device:
+        raise _lib.AvsiamHipError(f"mix_frames: need two uint8 [B, ..., 3, H, W] tensors of one shape on one device, got {tuple(v_u8.shape)} and {tuple(partner_u8.shape)}")
+    B = v_u8.shape[0]
+    plane = v_u8.shape[-1] * v_u8.shape[-2]
+    if B < 1 or plane < 1 or plane % 4:
+        raise _lib.AvsiamHipError(f"mix_frames: H * W = {plane} must be a positive multiple of 4, B = {B} positive")
+    n = v_u8.numel() // (3 * plane)
+    weight = _per_clip(weight, B, F32, "mix_frames.weight", v_u8.device)
+    if weight is None:
+        raise _lib.AvsiamHipError("mix_frames: weight is None")
+    if out is None:
+        out = torch.empty(v_u8.shape, dtype=F32, device=v_u8.device)
+    else:
+        _chk(out, F32, "mix_frames.out")
+        if out.shape != v_u8.shape or out.device != v_u8.device:
+            raise _lib.AvsiamHipError(f"mix_frames.out: expected {tuple(v_u8.shape)} on {v_u8.device}")
+    m3 = (ctypes.c_float * 3)(*[float(x) for x in mean])
+    s3 = (ctypes.c_float * 3)(*[float(x) for x in std])
+    _call("avs_mix_frames_u8", v_u8, partner_u8, weight, out, n, n // B, plane, ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), _stream())
+    return out

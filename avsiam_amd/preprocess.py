@@ -1,6 +1,11 @@
 """Input normalisation on the device - the per-sample host work of the reference dataloader
 (/root/reference/src/dataloader.py:505-513 audio, :461-462 + :152-155 frames) as two HBM-bound kernels, so that raw
-AudioSet-shaped tensors can be fed to ``CAVMAE_BASE.forward`` without a CPU pass.  No CPU fallback."""
+AudioSet-shaped tensors can be fed to ``CAVMAE_BASE.forward`` without a CPU pass.  No CPU fallback.
+
+Waveform input (the fine-tuning loader, dataloader_ft.py:277-340, 441-475): ``kaldi_fbank_reference`` is the float64 numpy SPECIFICATION of the device
+fbank (``ops.kaldi_fbank``, csrc/frontend.hip) - the Kaldi definition with the arguments of the reference's call, restated, not recorded:
+torchaudio was not available where this was written, so no golden from ``torchaudio.compliance.kaldi.fbank`` exists - and ``mixup_labels`` is
+the label side of mixup.  The frame side is ``ops.mix_frames``."""
 import ctypes
 
 import numpy as np
@@ -94,6 +99,110 @@ def draw_plan_reference(key, counter, B, T, F, freqm, timem, noise):
         shift, amp = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.float32)
     nk = int(philox4x32_10(c, 0, 0, 2, k0, k1)[()]) | (int(philox4x32_10(c, 1, 0, 2, k0, k1)[()]) << 32)
     return {"f0": f0, "fn": fn, "t0": t0, "tn": tn, "shift": shift.astype(np.int32), "amp": amp.astype(np.float32), "noise_key": nk}
+
+
+# ---- waveform input: the Kaldi fbank of the fine-tuning loader (dataloader_ft.py:277-340) -----------------------------------------------
+FBANK_FRAME, FBANK_SHIFT, FBANK_NFFT, FBANK_SR = 400, 160, 512, 16000
+FLT_EPSILON = 1.1920929e-07
+FBANK_FLOOR = np.float32(np.log(np.float64(np.float32(FLT_EPSILON))))        # -15.942385: what an energy at or below FLT_EPSILON becomes
+
+
+def fbank_frames(n):
+    """frames of an n-sample clip under snip_edges=True, 25 ms / 10 ms at 16 kHz"""
+    return 1 + (int(n) - FBANK_FRAME) // FBANK_SHIFT if n >= FBANK_FRAME else 0
+
+
+def fbank_mel_weights(n_mels=128):
+    """[n_mels, 257] float64 triangles of the Kaldi definition (htk_compat changes nothing without use_energy): mel(f) = 1127 ln(1 + f / 700),
+    low 20 Hz, high Nyquist, evaluated at the mel of every FFT bin; bin 256 has weight 0.  At 128 filters filter 3 holds no bin."""
+    mel = lambda f: 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+    lo, hi = mel(20.0), mel(FBANK_SR / 2)
+    delta = (hi - lo) / (n_mels + 1)
+    left = lo + np.arange(n_mels, dtype=np.float64)[:, None] * delta
+    centre = left + delta
+    right = centre + delta
+    m = mel((FBANK_SR / FBANK_NFFT) * np.arange(FBANK_NFFT // 2))[None, :]
+    w = np.maximum(0.0, np.minimum((m - left) / delta, (right - m) / delta))
+    return np.concatenate([w, np.zeros((n_mels, 1))], axis=1)
+
+
+def kaldi_fbank_reference(wave, lengths=None, partner=None, partner_lengths=None, lam=None, target_length=1024, n_mels=128, norm=None,
+                          dtype=np.float64, return_energy=False):
+    """The specification of ``ops.kaldi_fbank`` in numpy: torchaudio.compliance.kaldi.fbank(htk_compat=True, sample_frequency=16000,
+    use_energy=False, window_type='hanning', num_mel_bins=n_mels, dither=0.0, frame_shift=10) with torchaudio's other defaults (25 ms frames,
+    preemphasis 0.97, remove_dc_offset, round_to_power_of_two, snip_edges, low_freq 20, high_freq Nyquist, power, log), restated from the Kaldi
+    definition - torchaudio itself was never available to record from - plus what the loader does around it (dataloader_ft.py:277-340).
+
+    wave [B, S] (or [S]); lengths [B] samples per clip (None: S), each >= 400 (ValueError otherwise; the reference's try/except constant is not
+    reproduced).  Plain clip: w - mean(w).  Mixed clip (partner given and lam[b] >= 0): a = w1 - mean(w1), c = w2 - mean(w2) over the
+    partner's own length, THEN zero-padded or cut to the clip's length, mix = lam a + (1 - lam) c, the waveform is mix - mean(mix).
+    Frames: m = 1 + (n - 400) // 160; per frame: subtract the mean, y[i] = x[i] - 0.97 x[max(i - 1, 0)], Hann 0.5 - 0.5 cos(2 pi i / 399),
+    zero-pad to 512, |rfft|^2, the mel triangles, ln(max(E, FLT_EPSILON)).  Rows m .. target_length - 1 are 0, frames beyond are cut.
+    norm=(mean, std): (out - mean) / std on every row, pad rows included.  dtype=np.float32 runs the same steps in single precision
+    (scipy.fft keeps float32): what plain fp32 arithmetic gets.  -> [B, target_length, n_mels] of `dtype`; with return_energy also the mel
+    energies E before floor and log (same shape, pad rows 0), the quantity the kernel's energy-domain error is measured against."""
+    import scipy.fft
+    dt = np.dtype(dtype).type
+    wave = np.asarray(wave)
+    if wave.ndim == 1:
+        wave = wave[None]
+    B, S = wave.shape
+    lengths = np.full(B, S, dtype=np.int64) if lengths is None else np.asarray(lengths, dtype=np.int64).reshape(B)
+    if partner is not None:
+        partner = np.asarray(partner)
+        partner = partner[None] if partner.ndim == 1 else partner
+        partner_lengths = (np.full(B, partner.shape[1], dtype=np.int64) if partner_lengths is None
+                           else np.asarray(partner_lengths, dtype=np.int64).reshape(B))
+    lam = None if (lam is None or partner is None) else np.asarray(lam, dtype=np.float64).reshape(B)
+    if (lengths < FBANK_FRAME).any() or (lengths > S).any():
+        raise ValueError(f"kaldi_fbank: every clip needs 400 .. {S} samples, got lengths {lengths.tolist()}")
+    i = np.arange(FBANK_FRAME, dtype=np.float64)
+    window = (0.5 - 0.5 * np.cos(2.0 * np.pi * i / (FBANK_FRAME - 1))).astype(dt)
+    melw = fbank_mel_weights(n_mels).astype(dt)
+    out = np.zeros((B, target_length, n_mels), dtype=dt)
+    energies = np.zeros((B, target_length, n_mels), dtype=dt)
+    for b in range(B):
+        n = int(lengths[b])
+        w = wave[b, :n].astype(dt)
+        w = w - w.mean(dtype=dt)
+        if lam is not None and lam[b] >= 0:
+            n2 = int(partner_lengths[b])
+            if not 1 <= n2 <= partner.shape[1]:
+                raise ValueError(f"kaldi_fbank: partner length {n2} outside 1 .. {partner.shape[1]}")
+            w2 = partner[b, :n2].astype(dt)
+            w2 = w2 - w2.mean(dtype=dt)
+            c = np.zeros(n, dtype=dt)
+            c[:min(n, n2)] = w2[:n]
+            mix = dt(lam[b]) * w + (dt(1.0) - dt(lam[b])) * c
+            w = mix - mix.mean(dtype=dt)
+        m = min(fbank_frames(n), target_length)
+        idx = FBANK_SHIFT * np.arange(m)[:, None] + np.arange(FBANK_FRAME)[None, :]
+        fr = w[idx]
+        fr = fr - fr.mean(axis=1, keepdims=True, dtype=dt)
+        fr = (fr - dt(0.97) * np.concatenate([fr[:, :1], fr[:, :-1]], axis=1)) * window
+        spec = scipy.fft.rfft(fr, n=FBANK_NFFT, axis=1)
+        power = (spec.real * spec.real + spec.imag * spec.imag).astype(dt)
+        energy = power @ melw.T
+        energies[b, :m] = energy
+        out[b, :m] = np.log(np.maximum(energy, dt(FLT_EPSILON)))
+    if norm is not None:
+        out = ((out - dt(norm[0])) / dt(norm[1])).astype(dt)
+    return (out, energies) if return_energy else out
+
+
+def mixup_labels(y1_hot, y2_hot, lam, label_smooth):
+    """Labels of the fine-tuning loader (torch).  y1_hot / y2_hot [B, C] multi-hot (0 / 1), lam [B] (or a float), label_smooth s.  Mixed rows
+    (lam >= 0): s / C + lam (1 - s) hot1 + (1 - lam) (1 - s) hot2 (dataloader_ft.py:470-475); rows with lam < 0 (or y2_hot None): the plain
+    smoothed labels, 1 - s on the positives and s / C elsewhere (:480, :524)."""
+    y1 = y1_hot.to(torch.float32)
+    B, C = y1.shape
+    lam = torch.as_tensor(lam, dtype=torch.float32, device=y1.device).expand(B).reshape(B, 1)
+    s = float(label_smooth)
+    plain = torch.where(y1 > 0.5, torch.full_like(y1, 1.0 - s), torch.full_like(y1, s / C))
+    if y2_hot is None:
+        return plain
+    mixed = s / C + lam * (1.0 - s) * y1 + (1.0 - lam) * (1.0 - s) * y2_hot.to(torch.float32)
+    return torch.where(lam >= 0, mixed, plain)
 
 
 def normalize_frames(frames_u8, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD):

@@ -7,10 +7,17 @@ Data flags behave as in the pre-training entry point: --data_train '' or 'synthe
 label-smoothed multi-hot labels (the json/wav/mp4 pipeline is out of scope on this path).  --pretrain_path loads a CAVMAE_BASE checkpoint
 (with or without the 'module.' prefix) with strict=False (:243-249).  --freqm / --timem / --noise are the reference's training augmentation
 (dataloader_ft.py:527-548: SpecAugment masks on the un-normalised fbank, normalisation, noise, time roll), drawn per step on the device and
-applied inside the audio patch gather; validation never augments.  Accepted but not implemented: --mixup, --wa (weight averaging) and --bal - a
-warning names each one set to a non-default value (mixup: the reference mixes waveforms before the fbank, frames with a second weight, and
-draws the partner from the whole dataset - not reproducible from a batch of spectrograms); --warmup, distillation weights and logging are
-inert.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
+applied inside the audio patch gather; validation never augments.  Accepted but not implemented: --wa (weight averaging), --bal, and --mixup
+without --wave-input - a warning names each one set to a non-default value (mixup: the reference mixes waveforms before the fbank, frames with
+a second weight, and draws the partner from the whole dataset - not reproducible from a batch of spectrograms); --warmup, distillation
+weights and logging are inert.  Validation uses 10-frame synthetic clips when the test mode is mm_grad.
+--wave-input: the loaders yield what a decoder produces - float32 16 kHz waveforms (9 - 10 s, so the padding to 1024 rows is exercised) and
+uint8 frames - and the Kaldi fbank (dataloader_ft.py:325), its normalisation and, with --mixup p, the reference's mixup run on the device:
+waveforms mixed inside the fbank kernel's sample read (:308-322), frames with an independent weight (:457-458), labels as :470-475; the
+per-sample draws (mixed with probability p, lambda ~ Beta(10, 10), the frame weight) stay on the host, seeded per rank.  --freqm / --timem /
+--noise then act on the normalised fbank with fill (0 - mean) / std, which is the reference's SpecAugment -> normalise -> noise -> roll.
+Not built: wav / mp4 decoding, resampling, and choosing the partner from a dataset (the synthetic partner is the batch rolled by one).
+Refused together with --raw-input.
 Extensions: --raw-input (the loaders yield un-normalised fbank and uint8 frames, normalised on the device inside the kernels that read
 them, as in the pre-training launcher); --steps-per-epoch / --val-steps (synthetic epoch lengths); --device-metrics: the validation metrics come from the HIP counting
 kernel and the [N, C] outputs never leave the device (traintest_ft_base.calculate_stats_device; AP then groups tied scores as sklearn does);
@@ -91,6 +98,8 @@ def build_parser():
     p.add_argument('--force-dp', dest="force_dp", action="store_true", help="issue the data-parallel collectives at world size 1 too")
     p.add_argument('--raw-input', dest="raw_input", action="store_true",
                    help="feed un-normalised fbank + uint8 frames and normalise on the device (dataloader_ft.py:534, 461-462)")
+    p.add_argument('--wave-input', dest="wave_input", action="store_true",
+                   help="feed float32 waveforms + uint8 frames: Kaldi fbank, normalisation and --mixup on the device (dataloader_ft.py:277-340, 441-475)")
     p.add_argument('--eval-frames', dest="eval_frames", action="store_true",
                    help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
     return p
@@ -139,12 +148,15 @@ MIXUP_REASON = ("mixup is not reproducible from a batch of spectrograms: the ref
 
 
 def inert_flag_warnings(args):
-    """-> the warning lines for flags this path accepts and ignores (--freqm / --timem / --noise are implemented and not among them)"""
-    inert = [f"--{k} {getattr(args, k)}" for k, off in (("mixup", 0), ("wa", False), ("bal", None)) if getattr(args, k) not in (off, 'None')]
+    """-> the warning lines for flags this path accepts and ignores (--freqm / --timem / --noise are implemented and not among them; nor is
+    --mixup under --wave-input, where the waveforms it mixes exist)"""
+    live_mixup = bool(getattr(args, "wave_input", False))
+    inert = [f"--{k} {getattr(args, k)}" for k, off in (("mixup", 0), ("wa", False), ("bal", None))
+             if getattr(args, k) not in (off, 'None') and not (k == "mixup" and live_mixup)]
     out = []
     if inert:
         out.append("WARNING: not implemented on this path, ignored: " + ", ".join(inert) + " - this run trains without them")
-    if getattr(args, "mixup", 0) not in (0, 'None'):
+    if getattr(args, "mixup", 0) not in (0, 'None') and not live_mixup:
         out.append("WARNING: " + MIXUP_REASON)
     return out
 
@@ -161,6 +173,11 @@ def main(argv=None):
         raise SystemExit(f"--ftmode {args.ftmode}: the trainable modes are audioonly, videoonly and mm_grad")
     if args.eval_frames and (args.ftmode_test or args.ftmode) != "mm_grad":
         raise SystemExit("--eval-frames scores the frames of multi-frame clips: it needs the mm_grad test mode (--ftmode_test mm_grad)")
+    if args.wave_input and args.raw_input:
+        raise SystemExit("--wave-input and --raw-input both name the loader's output (waveforms + uint8 frames | un-normalised fbank + uint8 frames): "
+                         "pass one of them")
+    if args.wave_input and not 0.0 <= args.mixup <= 1.0:
+        raise SystemExit(f"--mixup {args.mixup}: a probability")
     for w in inert_flag_warnings(args):
         print(w, flush=True)
     import random
@@ -198,11 +215,19 @@ def _run(args):
             comm = TorchDistComm(always=args.force_dp)
         model.set_distributed(args.world_size, args.rank, comm)
     dev = model.arena.p.device
-    train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
-                                     raw=args.raw_input)
     val_frames = 10 if (args.ftmode_test or args.ftmode) == "mm_grad" else 1          # validate() runs is_eval=True: mm_grad wants 10 frames
-    val_loader = SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank, label_smooth=args.label_smooth,
-                                   frames=val_frames, raw=args.raw_input)
+    if args.wave_input:
+        from .traintest_ft_base import SyntheticWaveFtLoader
+        norm = (args.dataset_mean, args.dataset_std)
+        train_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
+                                             mixup=args.mixup, norm=norm, train=True)
+        val_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank,
+                                           label_smooth=args.label_smooth, frames=val_frames, norm=norm, train=False)
+    else:
+        train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
+                                         raw=args.raw_input)
+        val_loader = SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank, label_smooth=args.label_smooth,
+                                       frames=val_frames, raw=args.raw_input)
     os.makedirs(args.exp_dir or ".", exist_ok=True)
     args.exp_dir = args.exp_dir or "."
     result = train(model, train_loader, val_loader, None, args)

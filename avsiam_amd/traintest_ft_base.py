@@ -4,13 +4,15 @@
 the three parameter groups, no host sync); ``train`` / ``validate`` keep the reference's signatures and returns, branch draw (:133-160), losses
 (:105-110), schedulers (:91-97), freeze_base (:68-71) and artefacts (models/audio_model.{epoch}.pth, best_audio_model.pth, result.csv).
 Deliberate differences: the reference's stray forward outside autocast (:143, which would also break every mode but mm_grad) is not
-reproduced; weight averaging (--wa) and mixup are not implemented.
+reproduced; weight averaging (--wa) is not implemented; mixup only from waveforms (below).
 Augmentation (dataloader_ft.py:527-548: SpecAugment masks, noise, time roll - training batches only): ``train`` draws one plan per step on the
 device (``model.draw_aug`` from args.freqm / timem / noise) and the step applies it inside the audio patch gather; ``validate`` and
 ``evaluate_frames`` never augment and never touch the draw state.  args.raw_input: the loaders yield un-normalised fbank and uint8 frames,
-normalised inside the gathers (args.dataset_mean / dataset_std).  Mixup stays out: the reference mixes waveforms before the fbank
-(dataloader_ft.py:321-325), mixes frames with a second weight (:457-458) and draws the partner from the whole dataset (:400-417) - none of
-that is a function of a [B, T, F] batch of spectrograms.
+normalised inside the gathers (args.dataset_mean / dataset_std).  Mixup is not a function of a [B, T, F] batch of spectrograms - the reference
+mixes waveforms before the fbank (dataloader_ft.py:321-325), mixes frames with a second weight (:457-458) and draws the partner from the whole
+dataset (:400-417) - so ``train`` itself never mixes: it lives where the waveforms are, in ``SyntheticWaveFtLoader`` (the launcher's
+--wave-input), which runs the device fbank (``ops.kaldi_fbank``: the mix inside its sample read), ``ops.mix_frames`` and
+``preprocess.mixup_labels`` and hands ``train`` the (a, v, labels) it always took.
 Data parallel (the model's set_distributed with an active comm; the reference wraps the model in DistributedDataParallel(
 find_unused_parameters=True), :91-92): every rank draws its own branch and trains on its own shard, the fused step sums the gradients in a
 rank-independent schedule and steps what any rank reached (CAVMAEFT_BASE.train_step); ``validate`` gathers the predictions and targets of
@@ -239,6 +241,65 @@ class SyntheticFtLoader:
     def __iter__(self):
         for _ in range(self.steps):
             yield self.a, self.v, self.y
+
+
+class SyntheticWaveFtLoader:
+    """What a decoder produces, synthetic (``--wave-input``): 16 kHz float32 waveforms [B, 160 000] with per-batch lengths drawn in 9.0 - 10.0 s
+    (so the padding to ``cfg.audio_len`` rows is exercised), uint8 frames [B, frames, 3, H, W] and multi-hot labels; with ``mixup`` p > 0 also
+    a partner clip per sample (the batch rolled by one; choosing partners from a dataset stays a real loader's job).  The per-sample draws stay
+    on the host, as in the reference's Dataset (dataloader_ft.py:420-424, 457): mixed with probability p, lambda ~ Beta(10, 10), an independent
+    uniform frame weight - from a numpy Generator seeded by ``seed`` (per rank); the B scalars travel with the batch.
+    Iterating runs the front end on the device and yields what ``train`` / ``validate`` take, (a, v, labels):
+      a       ``ops.kaldi_fbank(wave, lengths, partner=..., lam=..., norm=(mean, std))`` - the waveform mixup inside the kernel's sample read
+      v       ``ops.mix_frames`` (training with mixup) or ``preprocess.normalize_frames``
+      labels  ``preprocess.mixup_labels`` (:470-475; unmixed rows: the plain smoothed labels)
+    ``a`` is the NORMALISED fbank: ``train`` then applies SpecAugment / noise / roll through ``aug`` with fill = (0 - mean) / std - the
+    reference's order, SpecAugment on the un-normalised fbank, normalisation, noise, roll.  train=False (validation): lam None, no mixing."""
+
+    def __init__(self, cfg, batch_size, steps, n_class, device, seed=87, label_smooth=0.1, frames=1, mixup=0.0, norm=(-5.081, 4.4849), train=True,
+                 samples=160000):
+        g = torch.Generator().manual_seed(seed)
+        B = batch_size
+        self.wave = (torch.randn(B, samples, generator=g) * 0.1).to(device)
+        self.v = (torch.randn(B, frames, cfg.in_chans, cfg.img_size, cfg.img_size, generator=g) * 0.25 + 0.5).clamp(0, 1).mul(255).round().to(torch.uint8).to(device)
+        hot = (torch.rand(B, n_class, generator=g) < 0.02).float()
+        hot[torch.arange(B), torch.randint(0, n_class, (B,), generator=g)] = 1.0
+        self.hot = hot.to(device)
+        self.mixup = float(mixup) if train else 0.0
+        if self.mixup > 0:
+            self.wave2, self.v2, self.hot2 = (torch.roll(t, 1, 0).contiguous() for t in (self.wave, self.v, self.hot))
+        self.rng = np.random.default_rng(seed)
+        self.steps, self.samples, self.norm, self.label_smooth, self.T = steps, samples, norm, label_smooth, cfg.audio_len
+        self.last_draw = None
+
+    def __len__(self):
+        return self.steps
+
+    def draw(self):
+        """the host draws of one batch -> dict of numpy arrays: lengths (and partner_lengths, lam, weight under mixup; lam < 0: not mixed)"""
+        B = self.wave.shape[0]
+        d = {"lengths": self.rng.integers(int(0.9 * self.samples), self.samples + 1, B).astype(np.int32)}
+        if self.mixup > 0:
+            mixed = self.rng.random(B) < self.mixup
+            d["partner_lengths"] = self.rng.integers(int(0.9 * self.samples), self.samples + 1, B).astype(np.int32)
+            d["lam"] = np.where(mixed, self.rng.beta(10, 10, B), -1.0).astype(np.float32)
+            d["weight"] = np.where(mixed, self.rng.random(B), 1.0).astype(np.float32)
+        return d
+
+    def __iter__(self):
+        from . import ops, preprocess
+        for _ in range(self.steps):
+            d = self.last_draw = self.draw()
+            if self.mixup > 0:
+                a = ops.kaldi_fbank(self.wave, d["lengths"], partner=self.wave2, partner_lengths=d["partner_lengths"], lam=d["lam"],
+                                    target_length=self.T, norm=self.norm)
+                v = ops.mix_frames(self.v, self.v2, d["weight"])
+                y = preprocess.mixup_labels(self.hot, self.hot2, torch.from_numpy(d["lam"]).to(self.hot.device), self.label_smooth)
+            else:
+                a = ops.kaldi_fbank(self.wave, d["lengths"], target_length=self.T, norm=self.norm)
+                v = preprocess.normalize_frames(self.v)
+                y = preprocess.mixup_labels(self.hot, None, -1.0, self.label_smooth)
+            yield a, v, y
 
 
 class _LrHolder:

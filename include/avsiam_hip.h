@@ -252,6 +252,34 @@ int avs_normalize_audio(const float* in, float* out, int B, int T, int F, float 
                         const float* amp, unsigned long long seed, avs_stream_t stream);
 int avs_normalize_frames_u8(const uint8_t* in, float* out, int n_images, int plane, const float* mean3, const float* std3,
                             avs_stream_t stream);
+/* the frame side of mixup (dataloader_ft.py:441-458): out = weight_b n(in1) + (1 - weight_b) n(in2), n the arithmetic of avs_normalize_frames_u8,
+ * b = image / per_sample; weight: DEVICE array, one value per sample (n_images / per_sample of them).  weight_b = 1 gives the bytes of
+ * avs_normalize_frames_u8(in1). */
+int avs_mix_frames_u8(const uint8_t* in1, const uint8_t* in2, const float* weight, float* out, int n_images, int per_sample, int plane,
+                      const float* mean3, const float* std3, avs_stream_t stream);
+
+/* ---- waveform input (dataloader_ft.py:277-340): the Kaldi fbank of torchaudio.compliance.kaldi.fbank(htk_compat=True, sample_frequency=16000,
+ * use_energy=False, window_type='hanning', num_mel_bins=128, dither=0.0, frame_shift=10) and the waveform mixup in front of it, on the device.
+ * The specification is avsiam_amd.preprocess.kaldi_fbank_reference (float64).  Per clip b of n = len[b] samples (NULL: stride), n >= 400 (the
+ * caller's check; a shorter clip has no frame and gives pad rows only):
+ *   frames   m = 1 + (n - 400) / 160; frame j = samples [160 j, 160 j + 400); subtract the frame mean; y[i] = x[i] - 0.97 x[max(i - 1, 0)];
+ *            times 0.5 - 0.5 cos(2 pi i / 399); zero-pad to 512; power spectrum |FFT|^2 of bins 0..255
+ *   mel      128 triangles in mel(f) = 1127 ln(1 + f / 700) between 20 Hz and 8 kHz, evaluated at the bins' mel; summed in bin order
+ *   out      row j = ln(max(E, FLT_EPSILON)) (an energy at or below FLT_EPSILON gives fp32(ln(FLT_EPSILON)) = -15.942385 exactly);
+ *            rows m .. target_length - 1 are 0 (ZeroPad2d), frames beyond target_length are not computed;
+ *            use_norm: every row, pad rows included, becomes (value - mean) * (1.0f / std), the product in fp32
+ *   samples  plain (no partner, lam NULL or lam[b] < 0): w - mean(w).  Mixed: a = w1 - mean(w1); c = w2 - mean(w2) (its own length), then
+ *            zero-padded or cut to n; mix = lam a + (1 - lam) c; the samples are mix - mean(mix).  The means come from `sums`.
+ * avs_wave_sums: sums[b] = { sum w1 over n, sum w2 over n2, sum w2 over min(n, n2) } in fp64, one fixed-order reduction per clip (the last
+ * two are 0 without a partner).  avs_kaldi_fbank reads them; both run on `stream`, neither synchronises (the first avs_kaldi_fbank call
+ * on a device uploads the tables with a blocking copy).  No atomics: two calls give identical bytes.  n_mels other than 128 returns -2.
+ * avs_fbank_tables: the host tables (fp64 rounded once to fp32) in the layout of csrc/frontend_math.h, FB_TAB_WORDS = 2960 words. */
+int avs_wave_sums(const float* wave, long long stride, const int* len, const float* partner, long long partner_stride,
+                  const int* partner_len, int B, double* sums, avs_stream_t stream);
+int avs_kaldi_fbank(const float* wave, long long stride, const int* len, const float* partner, long long partner_stride,
+                    const int* partner_len, const float* lam, const double* sums, int B, int target_length, int n_mels, float* out,
+                    int use_norm, float mean, float std, avs_stream_t stream);
+int avs_fbank_tables(float* tab, int words);
 
 /* ---- raw inputs, fused.  The same dataset arithmetic as avs_normalize_* above, applied where the input
  * is READ - the patch gather of the embedding and the target gather of the reconstruction loss - so un-normalised fbank
