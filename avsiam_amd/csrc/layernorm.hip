@@ -47,15 +47,35 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    const float mean = wave_sum_dpp(s) * (1.0f / D);
-    float q = 0.f;
+    float mean = wave_sum_dpp(s) * (1.0f / D);
+    float q = 0.f, c = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
         q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+        if (F32IO) c += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float var = wave_sum_dpp(q) * (1.0f / D);
-    const float rs = 1.0f / sqrtf(var + eps);
+    float var = wave_sum_dpp(q) * (1.0f / D);
+    float rs = 1.0f / sqrtf(var + eps);
+    if (F32IO) {
+        // fp32 output (the final norms and the classifier head: few rows).  The fp32 row sum of D values rounds its last additions to ~2^-24
+        // of the SUM, so on a row whose mean is large beside its spread (50 +- 0.5) the mean is off by a few 1e-6 and every normalised value
+        // by that times rstd: 1.3e-5 of the row, above the 1e-5 an fp32 output is held to.  The mean of the centred values, one more
+        // reduction, IS that error.  It is taken off where it moves the normalised values by more than 2^-21 (wave-uniform, rare: the rows of
+        // a training step sit at ~2e-8 and keep their bits), which leaves at most 5e-7.
+        const float corr = wave_sum_dpp(c) * (1.0f / D);
+        if (fabsf(corr) * rs > 4.76837158e-7f) {
+            mean += corr;
+            q = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                v[i].x -= corr; v[i].y -= corr; v[i].z -= corr; v[i].w -= corr;
+                q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+            }
+            var = wave_sum_dpp(q) * (1.0f / D);
+            rs = 1.0f / sqrtf(var + eps);
+        }
+    }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const float4 g = gv[i], b = bv[i];
