@@ -11,6 +11,8 @@
 //                     (8 points per lane in registers, LDS between the passes), power, 128 mel sums in bin order (two filters per lane, their
 //                     <= 10 weights in registers), log, and one coalesced 512-byte row.  Rows past the clip's frames are pad rows.
 //   avs_mix_frames_u8 the frame side of mixup (:441-458): weight_b n(v1) + (1 - weight_b) n(v2), n = avs_normalize_frames_u8's arithmetic.
+//   avs_resize_frames_u8  decoded-size uint8 frames, ragged per clip, to the normalised and optionally mixed fp32 frames of the model (:136-139,
+//                     434-459): antialiased bicubic resize in one two-pass kernel, the intermediate in LDS (described where it stands, below).
 //
 // Twiddles, window and mel weights are tables computed on the host in float64, rounded once and uploaded once per device (frontend_math.h);
 // no sincosf, no fast-math intrinsic, logf for the log.  No atomics: every output is bit-identical from call to call.
@@ -331,5 +333,269 @@ extern "C" int avs_mix_frames_u8(const uint8_t* in1, const uint8_t* in2, const f
     dim3 grid(n_images * 3, ceil_div(plane / 4, 256));
     mix_frames_kernel<<<grid, 256, 0, stream>>>(in1, in2, weight, out, plane, per_sample, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
     AVS_LAUNCH_CHECK("mix_frames");
+    return 0;
+}
+
+// ---- decoded-size frames: antialiased bicubic resize, normalisation, mix ---------------------------------------------------------------------
+// dataloader_ft.py:136-139, 434-459: frames / 255, Resize([224, 224], BICUBIC, antialias=True), Normalize, then the frame mix - from the uint8
+// frames of a decoder, each clip at its own size inside a padded buffer, to the fp32 tensor the model reads.  The specification is
+// preprocess.resize_frames_reference (float64); the taps are frontend_math.h's rz_taps, the same text on host and device.
+//
+// A workgroup of 8 waves owns `rows` output rows of one image, its three channels in turn.  Per channel and source (the clip, then its partner):
+//   taps        one thread per output column / output row evaluates its taps in double into LDS (x weights [tap][column], y weights [row][tap]);
+//               without a partner the three channels share them
+//   horizontal  the source rows the band needs go through LDS RZ_STAGE at a time, a wave per row, read as aligned dwords; a thread takes one
+//               output column of RZ_HB staged rows (each weight is read once for the four) and leaves sum_x wx (float)u8 in the LDS intermediate
+//   vertical    a thread takes four output columns of one output row: sum_y wy mid[y] on 16-byte LDS reads, normalised as normalize_frames_kernel
+//               does; the clip's result waits in LDS for the partner's, the mix is mix_frames_kernel's, the store one float4
+// Sums run in tap order in fp32.  The intermediate never leaves LDS; no atomics.  The host sizes `rows` and the LDS regions from the batch's
+// largest clip (rz_plan); sizes read on the device are cut to those maxima, so a wrong size array cannot index outside LDS or the buffer.
+#define RZ_THREADS 512
+#define RZ_STAGE 8                                         // source rows staged at a time: one per wave
+#define RZ_HB 4                                            // staged rows per thread of the horizontal pass
+#define RZ_LDS_LIMIT 98304                                 // the largest supported case (2240 x 2240 -> 224 x 224, one row per workgroup) takes 95.3 KB
+static_assert(RZ_THREADS == 64 * RZ_STAGE && RZ_STAGE % RZ_HB == 0, "one wave per staged row");
+
+struct RzSrc {
+    const uint8_t* p;                // [N, 3, Hs, Ws]
+    const int* sizes;                // [B, 2] (h, w) per clip, or NULL: (Hs, Ws)
+    int Hs, Ws, max_h, max_w;        // max_*: the largest clip of the batch, <= (Hs, Ws): what the LDS regions were sized for
+    size_t bytes;                    // of the whole buffer: the dword reads of a row's ends stay inside it
+};
+
+struct RzGeo {
+    int out_h, out_w, per_sample;
+    int rows, tcx, tcy, row_cap, sw; // output rows per workgroup | tap capacity per axis | rows of the intermediate | bytes per staged row
+    int mixed;
+};
+
+struct RzPlan {
+    int rows, tcx, tcy, row_cap, sw;
+    int lds_plain, lds_mixed;
+};
+
+// LDS regions, in this order: intermediate [row_cap][out_w] | clip's result [rows][out_w] (mixed only) | wx [tcx][out_w] | wy [rows][tcy] |
+// x start, x count [out_w] each | y start, y count [rows] each | staged rows [RZ_STAGE][sw]
+static int rz_lds_bytes(int out_w, int rows, int tcx, int tcy, int row_cap, int sw, bool mixed) {
+    return 4 * (row_cap * out_w + (mixed ? rows * out_w : 0) + tcx * out_w + rows * tcy + 2 * out_w + 2 * rows) + RZ_STAGE * sw;
+}
+
+// the most output rows per workgroup whose regions (the mixed form's) fit RZ_LDS_LIMIT; -> 0, or -1 when not even one row fits
+static int rz_plan(int max_h, int max_w, int out_h, int out_w, RzPlan* p) {
+    p->tcx = rz_tap_cap(max_w, out_w);
+    p->tcy = rz_tap_cap(max_h, out_h);
+    p->sw = ((max_w + 6) / 4) * 4;                          // a row keeps its byte offset in its first dword (0..3) and ends on a whole dword
+    for (int rows = 32; rows >= 1; rows >>= 1) {
+        p->rows = rows;
+        p->row_cap = rz_row_cap(max_h, out_h, rows);
+        p->lds_plain = rz_lds_bytes(out_w, rows, p->tcx, p->tcy, p->row_cap, p->sw, false);
+        p->lds_mixed = rz_lds_bytes(out_w, rows, p->tcx, p->tcy, p->row_cap, p->sw, true);
+        if (p->lds_mixed <= RZ_LDS_LIMIT) return 0;
+    }
+    return -1;
+}
+
+// grid (N, ceil(out_h / rows)), 512 threads, dynamic LDS
+__global__ __launch_bounds__(RZ_THREADS) void resize_frames_kernel(RzSrc A, RzSrc B, const float* __restrict__ weight, float* __restrict__ out, RzGeo G,
+                                                                   float m0, float m1, float m2, float s0, float s1, float s2) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rz_lds[];
+    float* __restrict__ s_mid = reinterpret_cast<float*>(rz_lds);
+    float* __restrict__ s_res = s_mid + G.row_cap * G.out_w;
+    float* __restrict__ s_wx = s_res + (G.mixed ? G.rows * G.out_w : 0);
+    float* __restrict__ s_wy = s_wx + G.tcx * G.out_w;
+    int* __restrict__ s_xs = reinterpret_cast<int*>(s_wy + G.rows * G.tcy);
+    int* __restrict__ s_xn = s_xs + G.out_w;
+    int* __restrict__ s_ys = s_xn + G.out_w;
+    int* __restrict__ s_yn = s_ys + G.rows;
+    uint8_t* __restrict__ s_stage = reinterpret_cast<uint8_t*>(s_yn + G.rows);
+
+    const int img = blockIdx.x, b = img / G.per_sample;
+    const int y0 = blockIdx.y * G.rows, nrows = min(G.rows, G.out_h - y0);       // >= 1 by the grid
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int ow = G.out_w, ow4 = ow >> 2;
+
+    // channel by channel; with a partner the clip, then the partner, of each.  Without one the taps of the first channel serve all three
+    for (int cs = 0; cs < 3 * (G.mixed + 1); ++cs) {
+        const int c = G.mixed ? cs >> 1 : cs, src = G.mixed ? cs & 1 : 0;
+        const RzSrc& S = src ? B : A;
+        int h = S.sizes ? S.sizes[2 * b] : S.Hs, w = S.sizes ? S.sizes[2 * b + 1] : S.Ws;
+        h = max(1, min(h, S.max_h));
+        w = max(1, min(w, S.max_w));
+
+        // taps.  Rows are kept relative to the band's first source row; a count is cut where the intermediate ends (never, by rz_row_cap)
+        int unused;
+        const int row0 = rz_span(h, G.out_h, y0, &unused);
+        for (int i = tid; i < ow + nrows && (G.mixed || c == 0); i += RZ_THREADS) {
+            int start;
+            if (i < ow) {
+                s_xn[i] = rz_taps(w, ow, i, G.tcx, &start, s_wx + i, ow);
+                s_xs[i] = start;
+            } else {
+                const int y = i - ow;
+                const int n = rz_taps(h, G.out_h, y0 + y, G.tcy, &start, s_wy + y * G.tcy, 1);
+                s_ys[y] = min(start - row0, G.row_cap);
+                s_yn[y] = max(0, min(n, row0 + G.row_cap - start));
+            }
+        }
+        __syncthreads();
+        const int rows_in = s_ys[nrows - 1] + s_yn[nrows - 1];                  // starts and ends do not decrease with the output row
+
+        const uint8_t* lo = S.p;
+        const uint8_t* hi = S.p + S.bytes;
+        const int nc = img * 3 + c;
+        const float mean = c == 0 ? m0 : c == 1 ? m1 : m2;
+        const float inv = 1.0f / (c == 0 ? s0 : c == 1 ? s1 : s2);
+        const uint8_t* __restrict__ plane = S.p + (size_t)nc * S.Hs * S.Ws;
+        for (int c0 = 0; c0 < rows_in; c0 += RZ_STAGE) {
+            // stage: wave wv reads source row row0 + c0 + wv as the aligned dwords that cover its w bytes
+            if (c0 + wv < rows_in) {
+                const uint8_t* rowp = plane + (size_t)(row0 + c0 + wv) * S.Ws;
+                const int off = (int)(reinterpret_cast<uintptr_t>(rowp) & 3);
+                const uint8_t* a0 = rowp - off;
+                const int ndw = (off + w + 3) >> 2;                             // 4 ndw <= w + 6: within sw
+                uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(s_stage + wv * G.sw);
+                for (int d = lane; d < ndw; d += 64) {
+                    const uint8_t* a = a0 + 4 * d;
+                    uint32_t v = 0;
+                    if (a >= lo && a + 4 <= hi) {
+                        v = *reinterpret_cast<const uint32_t*>(a);
+                    } else {                                                    // the buffer's first / last dword when its ends are not aligned
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (a + k >= lo && a + k < hi) v |= (uint32_t)a[k] << (8 * k);
+                    }
+                    dst[d] = v;
+                }
+            }
+            __syncthreads();
+            // horizontal: thread -> (group of RZ_HB staged rows, output column)
+            for (int it = tid; it < ow * (RZ_STAGE / RZ_HB); it += RZ_THREADS) {
+                const int g = it / ow, x = it - g * ow;
+                const int xs = s_xs[x], xn = s_xn[x];
+                const uint8_t* sp[RZ_HB];
+                float acc[RZ_HB];
+#pragma unroll
+                for (int q = 0; q < RZ_HB; ++q) {
+                    const int k = g * RZ_HB + q;
+                    const int off = (int)(reinterpret_cast<uintptr_t>(plane + (size_t)(row0 + c0 + k) * S.Ws) & 3);
+                    sp[q] = s_stage + k * G.sw + off + xs;
+                    acc[q] = 0.f;
+                }
+                for (int j = 0; j < xn; ++j) {
+                    const float wt = s_wx[j * ow + x];
+#pragma unroll
+                    for (int q = 0; q < RZ_HB; ++q) acc[q] += wt * (float)sp[q][j];
+                }
+#pragma unroll
+                for (int q = 0; q < RZ_HB; ++q) {
+                    const int r = c0 + g * RZ_HB + q;
+                    if (r < rows_in) s_mid[r * ow + x] = acc[q];                // (a row past rows_in was computed from stale bytes and is dropped)
+                }
+            }
+            __syncthreads();
+        }
+
+        // vertical, normalisation, mix: thread -> (output row, four columns)
+        for (int it = tid; it < nrows * ow4; it += RZ_THREADS) {
+            const int y = it / ow4, x4 = it - y * ow4;
+            const int yn = s_yn[y];
+            const float4* __restrict__ mid = reinterpret_cast<const float4*>(s_mid) + s_ys[y] * ow4 + x4;
+            const float* __restrict__ wy = s_wy + y * G.tcy;
+            float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+            for (int j = 0; j < yn; ++j) {
+                const float wt = wy[j];
+                const float4 v = mid[j * ow4];
+                r0 += wt * v.x; r1 += wt * v.y; r2 += wt * v.z; r3 += wt * v.w;
+            }
+            // normalize_frames_kernel's (x * (1.0f / 255.0f) - mean) * inv and mix_frames_kernel's w * a + u * b, with the contractions the compiler
+            // gives those two kernels spelled out (fma(x, 1 / 255, -mean) * inv; fma(u, b, w * a)): left to the compiler the same expressions
+            // come out of this kernel as separate multiplies and adds, and a clip at the output size would differ from them in the last bit
+            float4 o;
+            o.x = fmaf(r0, 1.0f / 255.0f, -mean) * inv;
+            o.y = fmaf(r1, 1.0f / 255.0f, -mean) * inv;
+            o.z = fmaf(r2, 1.0f / 255.0f, -mean) * inv;
+            o.w = fmaf(r3, 1.0f / 255.0f, -mean) * inv;
+            if (G.mixed && src == 0) {
+                reinterpret_cast<float4*>(s_res)[it] = o;    // read back by this thread
+            } else {
+                if (G.mixed) {
+                    const float wgt = weight[b], u = 1.0f - wgt;
+                    const float4 a = reinterpret_cast<const float4*>(s_res)[it];
+                    // weight 1: 1 * a + 0 * b = a, the bytes of the plain path
+                    o = make_float4(fmaf(u, o.x, wgt * a.x), fmaf(u, o.y, wgt * a.y), fmaf(u, o.z, wgt * a.z), fmaf(u, o.w, wgt * a.w));
+                }
+                *reinterpret_cast<float4*>(out + ((size_t)nc * G.out_h + y0 + y) * ow + 4 * x4) = o;
+            }
+        }
+        __syncthreads();                                                        // the next pass's taps and intermediate replace these
+    }
+}
+
+extern "C" int avs_resize_taps(int in_size, int out_size, int* start, int* count, float* weights, int max_taps) {
+    AVS_CHECK_ARG(start && count && weights && in_size >= 1 && out_size >= 1 && max_taps >= 1, "resize_taps: bad arguments");
+    AVS_CHECK_ARG((long long)in_size <= (long long)RZ_MAX_SCALE * out_size, "resize_taps: %d -> %d: the scale is limited to %d", in_size, out_size, RZ_MAX_SCALE);
+    AVS_CHECK_ARG(max_taps >= rz_tap_cap(in_size, out_size), "resize_taps: %d -> %d can take %d taps per output index, max_taps is %d", in_size, out_size,
+                  rz_tap_cap(in_size, out_size), max_taps);
+    for (int i = 0; i < out_size; ++i) {
+        for (int j = 0; j < max_taps; ++j) weights[(size_t)i * max_taps + j] = 0.f;
+        count[i] = rz_taps(in_size, out_size, i, max_taps, start + i, weights + (size_t)i * max_taps, 1);
+    }
+    return 0;
+}
+
+static int rz_check_size(const char* who, int max_h, int max_w, int out_h, int out_w) {
+    AVS_CHECK_ARG(out_h >= 1 && out_h <= 65535 && out_w >= 4 && out_w <= 65535 && (out_w % 4) == 0, "%s: output %d x %d: out_w must be a multiple of 4", who, out_h, out_w);
+    AVS_CHECK_ARG(max_h >= 1 && max_w >= 1 && (long long)max_h <= (long long)RZ_MAX_SCALE * out_h && (long long)max_w <= (long long)RZ_MAX_SCALE * out_w,
+                  "%s: %d x %d -> %d x %d: sizes start at 1 and the scale per axis is limited to %d", who, max_h, max_w, out_h, out_w, RZ_MAX_SCALE);
+    return 0;
+}
+
+extern "C" int avs_resize_plan(int max_h, int max_w, int out_h, int out_w, int* rows_per_wg, int* lds_bytes) {
+    AVS_CHECK_ARG(rows_per_wg && lds_bytes, "resize_plan: NULL result pointers");
+    if (int rc = rz_check_size("resize_plan", max_h, max_w, out_h, out_w)) return rc;
+    RzPlan p;
+    AVS_CHECK_ARG(rz_plan(max_h, max_w, out_h, out_w, &p) == 0, "resize_plan: %d x %d -> %d x %d: one output row takes more than %d bytes of LDS", max_h, max_w,
+                  out_h, out_w, RZ_LDS_LIMIT);
+    *rows_per_wg = p.rows;
+    *lds_bytes = p.lds_mixed;
+    return 0;
+}
+
+extern "C" int avs_resize_frames_u8(const uint8_t* in1, int Hs, int Ws, const int* sizes, int max_h, int max_w, const uint8_t* in2, int Hs2, int Ws2,
+                                    const int* sizes2, int max_h2, int max_w2, const float* weight, float* out, int n_images, int per_sample, int out_h,
+                                    int out_w, const float* mean3, const float* std3, hipStream_t stream) {
+    AVS_CHECK_ARG(in1 && out && mean3 && std3 && n_images > 0 && per_sample > 0 && (n_images % per_sample) == 0 && (long long)n_images * 3 <= 0x7fffffffLL,
+                  "resize_frames: bad arguments (in1, out, mean3, std3; n_images a multiple of the images per sample)");
+    AVS_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "resize_frames: out must be 16-byte aligned");
+    AVS_CHECK_ARG(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "resize_frames: zero std");
+    AVS_CHECK_ARG(Hs >= 1 && Ws >= 1 && max_h <= Hs && max_w <= Ws, "resize_frames: the largest clip (%d x %d) must fit the buffer (%d x %d)", max_h, max_w, Hs, Ws);
+    if (int rc = rz_check_size("resize_frames", max_h, max_w, out_h, out_w)) return rc;
+    if (in2) {
+        AVS_CHECK_ARG(weight, "resize_frames: a partner needs a weight per clip");
+        AVS_CHECK_ARG(Hs2 >= 1 && Ws2 >= 1 && max_h2 <= Hs2 && max_w2 <= Ws2, "resize_frames: the partner's largest clip (%d x %d) must fit its buffer (%d x %d)",
+                      max_h2, max_w2, Hs2, Ws2);
+        if (int rc = rz_check_size("resize_frames (partner)", max_h2, max_w2, out_h, out_w)) return rc;
+    } else {
+        AVS_CHECK_ARG(!sizes2 && !weight && Hs2 == 0 && Ws2 == 0 && max_h2 == 0 && max_w2 == 0, "resize_frames: partner sizes / weight without a partner");
+    }
+    RzPlan p;
+    const int ph = in2 && max_h2 > max_h ? max_h2 : max_h, pw = in2 && max_w2 > max_w ? max_w2 : max_w;
+    AVS_CHECK_ARG(rz_plan(ph, pw, out_h, out_w, &p) == 0, "resize_frames: %d x %d -> %d x %d: one output row takes more than %d bytes of LDS", ph, pw, out_h, out_w,
+                  RZ_LDS_LIMIT);
+    static bool attr_done = false;
+    if (!attr_done) {                                      // above the 64 KiB a kernel gets without asking
+        if (hipFuncSetAttribute((const void*)resize_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RZ_LDS_LIMIT) != hipSuccess) {
+            avs_set_error("resize_frames: hipFuncSetAttribute failed");
+            return -1;
+        }
+        attr_done = true;
+    }
+    const RzSrc A{in1, sizes, Hs, Ws, max_h, max_w, (size_t)n_images * 3 * Hs * Ws};
+    const RzSrc B{in2, sizes2, Hs2, Ws2, max_h2, max_w2, in2 ? (size_t)n_images * 3 * Hs2 * Ws2 : 0};
+    const RzGeo G{out_h, out_w, per_sample, p.rows, p.tcx, p.tcy, p.row_cap, p.sw, in2 ? 1 : 0};
+    dim3 grid(n_images, ceil_div(out_h, p.rows));
+    resize_frames_kernel<<<grid, RZ_THREADS, in2 ? p.lds_mixed : p.lds_plain, stream>>>(A, B, weight, out, G, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
+                                                                                        std3[2]);
+    AVS_LAUNCH_CHECK("resize_frames");
     return 0;
 }

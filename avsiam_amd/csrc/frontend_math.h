@@ -1,6 +1,7 @@
-// Arithmetic of the Kaldi fbank front end (frontend.hip) that does not depend on where it runs: the shape constants, the host tables
-// (float64, rounded once to fp32) and one lane's share of a radix-8 Stockham pass of the 512-point FFT.  Host and device compile the
-// same text, so the index arithmetic of the kernel can be walked lane by lane on a CPU.
+// Arithmetic of the front end (frontend.hip) that does not depend on where it runs.  Kaldi fbank: the shape constants, the host tables
+// (float64, rounded once to fp32) and one lane's share of a radix-8 Stockham pass of the 512-point FFT.  Frame resize: the taps of the
+// antialiased bicubic filter (at the end of the file).  Host and device compile the same text, so the index arithmetic of the kernels can be
+// walked lane by lane on a CPU.
 #pragma once
 #include <math.h>
 
@@ -105,4 +106,68 @@ static inline int fb_build_tables(float* tab) {
         itab[FB_TAB_COUNT + k] = count;
     }
     return 0;
+}
+
+// ---- antialiased bicubic resize (torch interpolate(mode='bicubic', align_corners=False, antialias=True), what torchvision's Resize calls) --------
+// Per axis, input size I, output size O, all in float64: scale = I / O, s = max(scale, 1), support = 2 s; output index i has its centre at
+// scale (i + 0.5), takes the input indices [start, start + n) = [max(int(centre - support + 0.5), 0), min(int(centre + support + 0.5), I)) with
+// weights cubic((j + start - centre + 0.5) / s), a = -0.5, divided by their sum (added in tap order) and rounded once to fp32.
+// Every product and sum below is rounded on its own (no fused multiply-add): host, device and numpy give the same bits.
+#define RZ_MAX_TAPS 41               // 2 support + 1 at the largest scale
+#define RZ_MAX_SCALE 10              // in / out per axis: 1080p -> 224 is 8.6
+
+__host__ __device__ inline double rz_cubic(double x) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double ax = x < 0.0 ? -x : x;
+    if (ax < 1.0) return (1.5 * ax - 2.5) * ax * ax + 1.0;
+    if (ax < 2.0) return (((ax - 5.0) * ax + 8.0) * ax - 4.0) * -0.5;
+    return 0.0;
+}
+
+// first input index and tap count of output index i
+__host__ __device__ inline int rz_span(int in_size, int out_size, int i, int* count) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double scale = (double)in_size / (double)out_size, s = scale < 1.0 ? 1.0 : scale, support = 2.0 * s;
+    const double centre = scale * ((double)i + 0.5);
+    int start = (int)(centre - support + 0.5), end = (int)(centre + support + 0.5);
+    if (start < 0) start = 0;
+    if (end > in_size) end = in_size;
+    *count = end - start;
+    return start;
+}
+
+// taps of output index i: weight j goes to w[j * wstride], j < the returned count (cut at max_taps: callers size max_taps from the scale, see
+// rz_tap_cap, so nothing is cut within the supported range).  No local array: the weights are evaluated twice, once for their sum.
+__host__ __device__ inline int rz_taps(int in_size, int out_size, int i, int max_taps, int* start_out, float* w, int wstride) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    int n;
+    const int start = rz_span(in_size, out_size, i, &n);
+    if (n > max_taps) n = max_taps;
+    const double scale = (double)in_size / (double)out_size, s = scale < 1.0 ? 1.0 : scale;
+    const double centre = scale * ((double)i + 0.5);
+    double total = 0.0;
+    for (int j = 0; j < n; ++j) total += rz_cubic(((double)(j + start) - centre + 0.5) / s);
+    for (int j = 0; j < n; ++j) w[j * wstride] = (float)(rz_cubic(((double)(j + start) - centre + 0.5) / s) / total);
+    *start_out = start;
+    return n;
+}
+
+// no output index of an axis has more taps than this: end - start <= ceil(2 support) (one more against the rounding of the scale)
+static inline int rz_tap_cap(int in_size, int out_size) {
+    const double scale = (double)in_size / (double)out_size, s = scale < 1.0 ? 1.0 : scale;
+    const int cap = (int)ceil(4.0 * s) + 1;
+    return cap > RZ_MAX_TAPS ? RZ_MAX_TAPS : cap;
+}
+
+// input rows that `rows` consecutive output rows span: last end - first start <= scale (rows - 1) + 2 support + 1
+static inline int rz_row_cap(int in_size, int out_size, int rows) {
+    const double scale = (double)in_size / (double)out_size, s = scale < 1.0 ? 1.0 : scale;
+    const int cap = (int)ceil(scale * (rows - 1) + 4.0 * s) + 2;
+    return cap > in_size ? in_size : cap;
 }

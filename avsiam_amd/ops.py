@@ -1407,3 +1407,83 @@ def mix_frames(v_u8, partner_u8, weight, mean=(0.485, 0.456, 0.406), std=(0.229,
     s3 = (ctypes.c_float * 3)(*[float(x) for x in std])
     _call("avs_mix_frames_u8", v_u8, partner_u8, weight, out, n, n // B, plane, ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), _stream())
     return out
+
+
+RESIZE_MAX_SCALE = 10                                     # csrc/frontend_math.h
+
+
+def resize_plan(max_h, max_w, out_h, out_w):
+    """(output rows per workgroup, LDS bytes) of the resize launch for a batch whose largest clip is max_h x max_w (avs_resize_plan; host only)"""
+    rows, lds = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("avs_resize_plan", int(max_h), int(max_w), int(out_h), int(out_w), ctypes.cast(ctypes.byref(rows), ctypes.c_void_p),
+              ctypes.cast(ctypes.byref(lds), ctypes.c_void_p))
+    return rows.value, lds.value
+
+
+def _clip_sizes(x, B, Hs, Ws, out_h, out_w, name, dev):
+    """per-clip (h, w) of a padded frame buffer: host values only - the launch is planned from the largest.  -> (device int32 [B, 2] or None,
+    max h, max w)"""
+    if x is None:
+        hw = torch.tensor([[Hs, Ws]], dtype=torch.int64)
+    else:
+        if torch.is_tensor(x) and x.is_cuda:
+            raise _lib.AvsiamHipError(f"{name}: the clip sizes are host values (sequence, numpy array or CPU tensor): the launch is planned from the largest")
+        hw = torch.as_tensor(x).reshape(-1)
+        if hw.numel() != 2 * B:
+            raise _lib.AvsiamHipError(f"{name}: expected {B} (h, w) pairs, got {hw.numel()} values")
+        hw = hw.to(torch.int64).reshape(B, 2)
+    mh, mw = int(hw[:, 0].max()), int(hw[:, 1].max())
+    if int(hw.min()) < 1 or mh > Hs or mw > Ws:
+        raise ValueError(f"{name}: sizes must lie in 1 .. {Hs} x {Ws}, got {hw.tolist()}")
+    if mh > RESIZE_MAX_SCALE * out_h or mw > RESIZE_MAX_SCALE * out_w:
+        raise ValueError(f"{name}: {mh} x {mw} -> {out_h} x {out_w}: the scale per axis is limited to {RESIZE_MAX_SCALE}")
+    return (None if x is None else hw.to(I32).to(dev)), mh, mw
+
+
+def resize_frames(v_u8, sizes=None, *, partner=None, partner_sizes=None, weight=None, size=224, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
+                  out=None):
+    """Decoded-size uint8 frames to the model's fp32 frames in one launch (avs_resize_frames_u8; the specification is
+    preprocess.resize_frames_reference): / 255, torchvision Resize(size, BICUBIC, antialias=True) - torch's interpolate(mode='bicubic',
+    align_corners=False, antialias=True), no clamping -, Normalize(mean, std) and, with a partner, the frame mix (dataloader_ft.py:136-139, 434-459).
+
+    v_u8 uint8 [B, 3, Hs, Ws] or [B, F, 3, Hs, Ws], a padded buffer: clip b fills the top-left sizes[b] = (h, w) corner.  sizes / partner_sizes:
+    HOST values ([B, 2] sequence, numpy array or CPU tensor; None: the buffer's size), range-checked (ValueError) and uploaded - a device tensor
+    is refused, the launch is planned from the largest clip.  1 <= h <= Hs, 1 <= w <= Ws, at most 10 x the output per axis.  partner: its own
+    buffer [B, (F,) 3, Hs2, Ws2] and sizes; weight [B] fp32 as in mix_frames (device tensor, or host values that are uploaded): out = weight_b n(r)
+    + (1 - weight_b) n(r_partner).  size: int or (out_h, out_w), out_w % 4 == 0.
+    -> fp32 [B, (F,) 3, out_h, out_w].  A clip at the output size gives normalize_frames' bytes, weight 1 the plain call's; no atomics: two calls
+    give identical bytes."""
+    _chk(v_u8, U8, "resize_frames.v"); _chk(partner, U8, "resize_frames.partner")
+    if v_u8.dim() not in (4, 5) or v_u8.shape[-3] != 3 or v_u8.shape[0] < 1 or v_u8.numel() == 0:
+        raise _lib.AvsiamHipError(f"resize_frames: need uint8 [B, 3, H, W] or [B, F, 3, H, W], got {tuple(v_u8.shape)}")
+    dev, B = v_u8.device, v_u8.shape[0]
+    Hs, Ws = v_u8.shape[-2:]
+    out_h, out_w = (int(size[0]), int(size[1])) if hasattr(size, "__len__") else (int(size), int(size))
+    if out_h < 1 or out_w < 4 or out_w % 4:
+        raise _lib.AvsiamHipError(f"resize_frames: output {out_h} x {out_w}: out_w must be a positive multiple of 4")
+    if partner is None and (partner_sizes is not None or weight is not None):
+        raise _lib.AvsiamHipError("resize_frames: partner_sizes / weight without a partner")
+    if partner is not None and (partner.dim() != v_u8.dim() or partner.shape[:-2] != v_u8.shape[:-2] or partner.device != dev or partner.numel() == 0):
+        raise _lib.AvsiamHipError(f"resize_frames: partner {tuple(partner.shape)} on {partner.device} does not match frames {tuple(v_u8.shape)} on {dev}")
+    n = v_u8.numel() // (3 * Hs * Ws)
+    sizes, mh, mw = _clip_sizes(sizes, B, Hs, Ws, out_h, out_w, "resize_frames.sizes", dev)
+    Hs2 = Ws2 = mh2 = mw2 = 0
+    if partner is not None:
+        Hs2, Ws2 = partner.shape[-2:]
+        partner_sizes, mh2, mw2 = _clip_sizes(partner_sizes, B, Hs2, Ws2, out_h, out_w, "resize_frames.partner_sizes", dev)
+        weight = _per_clip(weight, B, F32, "resize_frames.weight", dev)
+        if weight is None:
+            raise _lib.AvsiamHipError("resize_frames: a partner needs a weight per clip")
+    shape = tuple(v_u8.shape[:-2]) + (out_h, out_w)
+    if out is None:
+        out = torch.empty(shape, dtype=F32, device=dev)
+    else:
+        _chk(out, F32, "resize_frames.out")
+        if tuple(out.shape) != shape or out.device != dev:
+            raise _lib.AvsiamHipError(f"resize_frames.out: expected {shape} on {dev}, got {tuple(out.shape)} on {out.device}")
+    m3 = (ctypes.c_float * 3)(*[float(x) for x in mean])
+    s3 = (ctypes.c_float * 3)(*[float(x) for x in std])
+    nbytes = float(v_u8.numel() + (partner.numel() if partner is not None else 0) + 4 * out.numel())
+    _launch("resize_frames", (0.0, nbytes), "avs_resize_frames_u8", v_u8, Hs, Ws, sizes, mh, mw, partner, Hs2, Ws2, partner_sizes, mh2, mw2, weight, out, n,
+            n // B, out_h, out_w, ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), _stream())
+    return out

@@ -205,6 +205,102 @@ def mixup_labels(y1_hot, y2_hot, lam, label_smooth):
     return torch.where(lam >= 0, mixed, plain)
 
 
+# ---- decoded-size frames: the antialiased bicubic Resize of the fine-tuning loader (dataloader_ft.py:136-139, 434-459) ----------------------
+RESIZE_MAX_SCALE, RESIZE_MAX_TAPS = 10, 41
+
+
+def _resize_cubic(x):
+    """the cubic convolution kernel, a = -0.5, every product and sum rounded on its own in the order csrc/frontend_math.h's rz_cubic writes"""
+    ax = np.abs(x)
+    near = (1.5 * ax - 2.5) * ax * ax + 1.0
+    far = (((ax - 5.0) * ax + 8.0) * ax - 4.0) * -0.5
+    return np.where(ax < 1.0, near, np.where(ax < 2.0, far, 0.0))
+
+
+def resize_taps_reference(I, O):
+    """One axis of torch.nn.functional.interpolate(mode='bicubic', align_corners=False, antialias=True) from I to O samples, in float64:
+    scale = I / O, s = max(scale, 1), support = 2 s; output index i: centre = scale (i + 0.5), start = max(int(centre - support + 0.5), 0),
+    end = min(int(centre + support + 0.5), I), w_j = cubic((j + start - centre + 0.5) / s) for j < end - start, divided by their sum (added
+    in tap order).  -> (start int32 [O], count int32 [O], weights float64 [O, max count], zero beyond each count).  Rounded once to fp32 the
+    weights are the kernel's, bit for bit (avs_resize_taps)."""
+    I, O = int(I), int(O)
+    if I < 1 or O < 1:
+        raise ValueError(f"resize_taps: sizes {I} -> {O}")
+    scale = np.float64(I) / np.float64(O)
+    s = max(scale, np.float64(1.0))
+    support = 2.0 * s
+    start, count, rows = np.zeros(O, dtype=np.int32), np.zeros(O, dtype=np.int32), []
+    for i in range(O):
+        centre = scale * (np.float64(i) + 0.5)
+        lo, hi = max(int(centre - support + 0.5), 0), min(int(centre + support + 0.5), I)
+        w = _resize_cubic(((np.arange(lo, hi, dtype=np.float64) - centre) + 0.5) / s)
+        total = np.float64(0.0)
+        for v in w:
+            total = total + v
+        start[i], count[i] = lo, hi - lo
+        rows.append(w / total)
+    weights = np.zeros((O, int(count.max())), dtype=np.float64)
+    for i, w in enumerate(rows):
+        weights[i, :len(w)] = w
+    return start, count, weights
+
+
+def _resize_matrix(I, O, dtype):
+    """the taps of one axis as a dense [O, I] matrix (weights rounded to `dtype` first)"""
+    start, count, w = resize_taps_reference(I, O)
+    m = np.zeros((O, I), dtype=dtype)
+    for i in range(O):
+        m[i, start[i]:start[i] + count[i]] = w[i, :count[i]].astype(dtype)
+    return m
+
+
+def resize_frames_reference(frames_u8, sizes=None, partner=None, partner_sizes=None, weight=None, size=224, mean=IMAGENET_DEFAULT_MEAN,
+                            std=IMAGENET_DEFAULT_STD, dtype=np.float64):
+    """The specification of ``ops.resize_frames`` in numpy float64: what the reference's loader does to decoded frames
+    (dataloader_ft.py:136-139, 434-459), with torchvision's Resize restated from torch's interpolate (``resize_taps_reference``).
+
+    frames_u8 uint8 [B, 3, Hs, Ws] or [B, F, 3, Hs, Ws], a padded buffer: clip b fills the top-left sizes[b] = (h, w) corner (None: Hs x Ws);
+    what lies outside is never read.  size: int or (out_h, out_w).  Per clip and channel:
+      1. x = the clip's h x w pixels as float (the division by 255 comes after the resize, where the kernel has it: the filter is linear)
+      2. horizontal pass: r[y, i] = sum_j wx[i, j] x[y, start_x[i] + j]
+      3. vertical pass:   r[i, :] = sum_j wy[i, j] r[start_y[i] + j, :]            (no clamping: overshoot outside [0, 255] stays)
+      4. n(r) = (r / 255 - mean_c) / std_c
+      5. with a partner (its own buffer and sizes): weight_b n(r) + (1 - weight_b) n(r_partner)            (:457-458)
+    dtype=np.float32 runs the same steps with fp32 weights and fp32 sums.  -> [..., 3, out_h, out_w] of `dtype`."""
+    dt = np.dtype(dtype).type
+    out_h, out_w = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    mean, std = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+
+    def one(buf, szs):
+        buf = np.asarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim not in (4, 5) or buf.shape[-3] != 3:
+            raise ValueError(f"resize_frames: need uint8 [B, 3, H, W] or [B, F, 3, H, W], got {buf.dtype} {buf.shape}")
+        B, (Hs, Ws) = buf.shape[0], buf.shape[-2:]
+        szs = np.tile([[Hs, Ws]], (B, 1)) if szs is None else np.asarray(szs, dtype=np.int64).reshape(B, 2)
+        res = np.zeros(buf.shape[:-2] + (out_h, out_w), dtype=dt)
+        for b in range(B):
+            h, w = int(szs[b, 0]), int(szs[b, 1])
+            if not (1 <= h <= Hs and 1 <= w <= Ws) or h > RESIZE_MAX_SCALE * out_h or w > RESIZE_MAX_SCALE * out_w:
+                raise ValueError(f"resize_frames: clip {b} is {h} x {w}: sizes lie in 1 .. {Hs} x {Ws} and within {RESIZE_MAX_SCALE} times the output")
+            mx, my = _resize_matrix(w, out_w, dt), _resize_matrix(h, out_h, dt)
+            x = buf[b, ..., :h, :w].astype(dt)
+            r = np.matmul(my, np.matmul(x, mx.T))
+            n = (r / dt(255.0) - mean.astype(dt)[:, None, None]) / std.astype(dt)[:, None, None]
+            res[b] = n
+        return res
+
+    a = one(frames_u8, sizes)
+    if partner is None:
+        if partner_sizes is not None or weight is not None:
+            raise ValueError("resize_frames: partner_sizes / weight without a partner")
+        return a
+    c = one(partner, partner_sizes)
+    if c.shape != a.shape:
+        raise ValueError(f"resize_frames: the partner gives {c.shape}, the clips {a.shape}")
+    wgt = np.asarray(weight, dtype=dt).reshape((a.shape[0],) + (1,) * (a.ndim - 1))
+    return (wgt * a + (dt(1.0) - wgt) * c).astype(dt)
+
+
 def normalize_frames(frames_u8, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD):
     """frames [..., 3, H, W] uint8 (GPU) -> fp32 (x / 255 - mean_c) / std_c (dataloader.py:461-462 and my_normalize)."""
     if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() >= 3 and frames_u8.shape[-3] == 3

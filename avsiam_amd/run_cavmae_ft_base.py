@@ -18,6 +18,10 @@ per-sample draws (mixed with probability p, lambda ~ Beta(10, 10), the frame wei
 --noise then act on the normalised fbank with fill (0 - mean) / std, which is the reference's SpecAugment -> normalise -> noise -> roll.
 Not built: wav / mp4 decoding, resampling, and choosing the partner from a dataset (the synthetic partner is the batch rolled by one).
 Refused together with --raw-input.
+--frame-size H W (only with --wave-input): the loaders keep their uint8 frames at the decoded size H x W, every batch draws a size per clip (the
+full size or a narrower crop, so one padded buffer holds clips of several sizes) and ops.resize_frames runs what the reference's loader does
+to them (dataloader_ft.py:136-139, 434-459: / 255, Resize([224, 224], BICUBIC, antialias=True), Normalize, the frame mix) in one launch; H and W
+lie in 1 .. 2240 (at most 10 x the model's 224).  Not built: video decoding and frame selection.
 Extensions: --raw-input (the loaders yield un-normalised fbank and uint8 frames, normalised on the device inside the kernels that read
 them, as in the pre-training launcher); --steps-per-epoch / --val-steps (synthetic epoch lengths); --device-metrics: the validation metrics come from the HIP counting
 kernel and the [N, C] outputs never leave the device (traintest_ft_base.calculate_stats_device; AP then groups tied scores as sklearn does);
@@ -100,6 +104,9 @@ def build_parser():
                    help="feed un-normalised fbank + uint8 frames and normalise on the device (dataloader_ft.py:534, 461-462)")
     p.add_argument('--wave-input', dest="wave_input", action="store_true",
                    help="feed float32 waveforms + uint8 frames: Kaldi fbank, normalisation and --mixup on the device (dataloader_ft.py:277-340, 441-475)")
+    p.add_argument('--frame-size', dest="frame_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                   help="with --wave-input: uint8 frames at the decoded size H x W, resized (antialiased bicubic), normalised and mixed on the device "
+                        "(dataloader_ft.py:136-139, 434-459)")
     p.add_argument('--eval-frames', dest="eval_frames", action="store_true",
                    help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
     return p
@@ -178,6 +185,11 @@ def main(argv=None):
                          "pass one of them")
     if args.wave_input and not 0.0 <= args.mixup <= 1.0:
         raise SystemExit(f"--mixup {args.mixup}: a probability")
+    if args.frame_size is not None:
+        if not args.wave_input:
+            raise SystemExit("--frame-size names the size of the decoded uint8 frames of --wave-input: pass it with --wave-input")
+        if not all(1 <= x <= 2240 for x in args.frame_size):
+            raise SystemExit(f"--frame-size {args.frame_size[0]} {args.frame_size[1]}: H and W lie in 1 .. 2240 (at most 10 x the model's 224)")
     for w in inert_flag_warnings(args):
         print(w, flush=True)
     import random
@@ -220,9 +232,9 @@ def _run(args):
         from .traintest_ft_base import SyntheticWaveFtLoader
         norm = (args.dataset_mean, args.dataset_std)
         train_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
-                                             mixup=args.mixup, norm=norm, train=True)
+                                             mixup=args.mixup, norm=norm, train=True, frame_size=args.frame_size)
         val_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank,
-                                           label_smooth=args.label_smooth, frames=val_frames, norm=norm, train=False)
+                                           label_smooth=args.label_smooth, frames=val_frames, norm=norm, train=False, frame_size=args.frame_size)
     else:
         train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
                                          raw=args.raw_input)

@@ -254,14 +254,23 @@ class SyntheticWaveFtLoader:
       v       ``ops.mix_frames`` (training with mixup) or ``preprocess.normalize_frames``
       labels  ``preprocess.mixup_labels`` (:470-475; unmixed rows: the plain smoothed labels)
     ``a`` is the NORMALISED fbank: ``train`` then applies SpecAugment / noise / roll through ``aug`` with fill = (0 - mean) / std - the
-    reference's order, SpecAugment on the un-normalised fbank, normalisation, noise, roll.  train=False (validation): lam None, no mixing."""
+    reference's order, SpecAugment on the un-normalised fbank, normalisation, noise, roll.  train=False (validation): lam None, no mixing.
+    frame_size=(H, W): the uint8 frames stay at the decoded size [B, frames, 3, H, W]; every batch draws a size per clip (and per partner) from
+    FRAME_CROPS of (H, W) - the full frame or a narrower crop, so one padded buffer holds clips of several sizes - and ``v`` comes from
+    ``ops.resize_frames`` (:136-139, 434-459: / 255, antialiased bicubic Resize to the model's size, Normalize, the mix with ``weight``); the
+    sizes are in ``last_draw`` as ``sizes`` / ``partner_sizes``.  None: frames at the model's size, as above."""
+
+    FRAME_CROPS = ((1.0, 1.0), (1.0, 0.75))                  # (h, w) fractions of frame_size a clip's size is drawn from
 
     def __init__(self, cfg, batch_size, steps, n_class, device, seed=87, label_smooth=0.1, frames=1, mixup=0.0, norm=(-5.081, 4.4849), train=True,
-                 samples=160000):
+                 samples=160000, frame_size=None):
         g = torch.Generator().manual_seed(seed)
         B = batch_size
         self.wave = (torch.randn(B, samples, generator=g) * 0.1).to(device)
-        self.v = (torch.randn(B, frames, cfg.in_chans, cfg.img_size, cfg.img_size, generator=g) * 0.25 + 0.5).clamp(0, 1).mul(255).round().to(torch.uint8).to(device)
+        self.frame_size = None if frame_size is None else (int(frame_size[0]), int(frame_size[1]))
+        self.img_size = cfg.img_size
+        fh, fw = self.frame_size or (cfg.img_size, cfg.img_size)
+        self.v = (torch.randn(B, frames, cfg.in_chans, fh, fw, generator=g) * 0.25 + 0.5).clamp(0, 1).mul(255).round().to(torch.uint8).to(device)
         hot = (torch.rand(B, n_class, generator=g) < 0.02).float()
         hot[torch.arange(B), torch.randint(0, n_class, (B,), generator=g)] = 1.0
         self.hot = hot.to(device)
@@ -284,6 +293,11 @@ class SyntheticWaveFtLoader:
             d["partner_lengths"] = self.rng.integers(int(0.9 * self.samples), self.samples + 1, B).astype(np.int32)
             d["lam"] = np.where(mixed, self.rng.beta(10, 10, B), -1.0).astype(np.float32)
             d["weight"] = np.where(mixed, self.rng.random(B), 1.0).astype(np.float32)
+        if self.frame_size is not None:                      # (drawn last: the draws above are those of frame_size=None)
+            crops = np.array([[max(1, round(self.frame_size[0] * fh)), max(1, round(self.frame_size[1] * fw))] for fh, fw in self.FRAME_CROPS], dtype=np.int32)
+            d["sizes"] = crops[self.rng.integers(0, len(crops), B)]
+            if self.mixup > 0:
+                d["partner_sizes"] = crops[self.rng.integers(0, len(crops), B)]
         return d
 
     def __iter__(self):
@@ -293,11 +307,12 @@ class SyntheticWaveFtLoader:
             if self.mixup > 0:
                 a = ops.kaldi_fbank(self.wave, d["lengths"], partner=self.wave2, partner_lengths=d["partner_lengths"], lam=d["lam"],
                                     target_length=self.T, norm=self.norm)
-                v = ops.mix_frames(self.v, self.v2, d["weight"])
+                v = (ops.mix_frames(self.v, self.v2, d["weight"]) if self.frame_size is None else
+                     ops.resize_frames(self.v, d["sizes"], partner=self.v2, partner_sizes=d["partner_sizes"], weight=d["weight"], size=self.img_size))
                 y = preprocess.mixup_labels(self.hot, self.hot2, torch.from_numpy(d["lam"]).to(self.hot.device), self.label_smooth)
             else:
                 a = ops.kaldi_fbank(self.wave, d["lengths"], target_length=self.T, norm=self.norm)
-                v = preprocess.normalize_frames(self.v)
+                v = preprocess.normalize_frames(self.v) if self.frame_size is None else ops.resize_frames(self.v, d["sizes"], size=self.img_size)
                 y = preprocess.mixup_labels(self.hot, None, -1.0, self.label_smooth)
             yield a, v, y
 

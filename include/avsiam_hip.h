@@ -281,6 +281,30 @@ int avs_kaldi_fbank(const float* wave, long long stride, const int* len, const f
                     int use_norm, float mean, float std, avs_stream_t stream);
 int avs_fbank_tables(float* tab, int words);
 
+/* ---- decoded-size frames (dataloader_ft.py:136-139, 434-459): frames / 255, Resize([224, 224], BICUBIC, antialias=True), Normalize and the frame
+ * mix, from uint8 frames at the video's own size.  The specification is avsiam_amd.preprocess.resize_frames_reference (float64): torch's
+ * interpolate(mode='bicubic', align_corners=False, antialias=True), no clamping.  Per axis with input size I and output size O, in float64:
+ *   scale = I / O, s = max(scale, 1), support = 2 s; output index i: centre = scale (i + 0.5), start = max(int(centre - support + 0.5), 0),
+ *   end = min(int(centre + support + 0.5), I); w_j = cubic((j + start - centre + 0.5) / s), j < end - start, divided by their sum;
+ *   cubic(x), a = -0.5: |x| < 1: ((a + 2) |x| - (a + 3)) x^2 + 1; |x| < 2: (((|x| - 5) |x| + 8) |x| - 4) a; else 0.
+ * avs_resize_taps (host only, no GPU): start[out_size], count[out_size] and weights[out_size][max_taps] (rounded once to fp32, zero beyond the
+ * count) of one axis - the text the kernel runs (csrc/frontend_math.h); -2 when in_size > 10 out_size or max_taps is below what the scale can take.
+ * avs_resize_frames_u8: in1 uint8 [n_images, 3, Hs, Ws], a padded buffer: the images of clip b = image / per_sample fill the top-left
+ * sizes[2 b] x sizes[2 b + 1] corner (sizes: DEVICE int32 [B, 2], or NULL: Hs x Ws); max_h / max_w: the largest of them (host values; the
+ * launch is planned from them and a size beyond them is cut to them).  out fp32 [n_images, 3, out_h, out_w], 16-byte aligned, out_w % 4 == 0:
+ *   r = sum_y wy sum_x wx (float)u8 in fp32 in tap order, then n(r) = (r (1/255f) - mean_c) (1 / std_c) as avs_normalize_frames_u8 writes it.
+ * in2 (may be NULL, then Hs2 .. max_w2 are 0 and sizes2 / weight NULL): the partner, its own buffer and sizes; out = weight_b n(r1) +
+ * (1 - weight_b) n(r2) as avs_mix_frames_u8 (weight: DEVICE, one per clip).  A clip at the output size gives avs_normalize_frames_u8's bytes,
+ * weight 1 the plain call's.  1 <= h <= Hs, 1 <= w <= Ws, in / out <= 10 per axis (at most 41 taps: 1080p -> 224 is 8.6); anything else is -2
+ * before any launch.  One kernel, the horizontal pass's results stay in LDS; no atomics: two calls give identical bytes.  mean3 / std3: HOST.
+ * avs_resize_plan (host only): output rows per workgroup and the LDS bytes (of the call with a partner; without one rows * out_w * 4 fewer)
+ * the launch of a batch whose largest clip is max_h x max_w takes. */
+int avs_resize_taps(int in_size, int out_size, int* start, int* count, float* weights, int max_taps);
+int avs_resize_plan(int max_h, int max_w, int out_h, int out_w, int* rows_per_wg, int* lds_bytes);
+int avs_resize_frames_u8(const uint8_t* in1, int Hs, int Ws, const int* sizes, int max_h, int max_w, const uint8_t* in2, int Hs2, int Ws2,
+                         const int* sizes2, int max_h2, int max_w2, const float* weight, float* out, int n_images, int per_sample, int out_h,
+                         int out_w, const float* mean3, const float* std3, avs_stream_t stream);
+
 /* ---- raw inputs, fused.  The same dataset arithmetic as avs_normalize_* above, applied where the input
  * is READ - the patch gather of the embedding and the target gather of the reconstruction loss - so un-normalised fbank
  * and uint8 frames go straight from the loader's buffers into the model: one read of the raw tensor per consumer instead of
