@@ -1212,7 +1212,7 @@ class MaePass:
             self.pool.owner = self
         if plan is not None:
             self._set_plan(plan)
-        self.audio, self.imgs, self.xf = audio, _fold_frames(imgs, T), xf
+        self.audio, self.imgs, self.xf, self.imgs_shape = audio, _fold_frames(imgs, T), xf, tuple(imgs.shape)
         for st, lo, hi, fin, fstat, omap, rows, emb, blks in self.towers:
             emb.forward(audio if emb.audio else self.imgs, st.x[0][lo:hi], xf[0 if emb.audio else 1])
         for st in self.tower_stacks:
@@ -1253,6 +1253,31 @@ class MaePass:
         fa[ida] = pa
         fv[idv] = pv
         return fa.view(B, La, -1), fv.view(B, T * Lv, -1)
+
+    def reconstruct(self, paste_kept=True, raw=False):
+        """The last forward's predictions as pictures (unpatchify, cav_mae_base.py:353-363; csrc/inpaint.hip), on the device, nothing copied to
+        the host and no synchronisation: -> (audio [B, T, F], imgs in the shape forward() was given, err_a [B, La], err_v [B, T * Lv]).
+        paste_kept: the kept patches (mask 0) and the cells no patch covers are the input as the model saw it, bit for bit; False: every patch
+        is the decoder's prediction - every row must then have been predicted (EngineOptions.prune_dead off).  raw: in the units of the RAW
+        inputs the forward was given (un-normalised fbank, uint8 frames: the inverse of their ops.InputXf); a modality that came in
+        normalised stays as it is.  err_*: per-token mean squared error of the scored tokens (the loss kernel's row sums), 0 on kept ones."""
+        cfg, B = self.cfg, self.B
+        if getattr(self, "audio", None) is None:
+            raise RuntimeError("MaePass.reconstruct: no forward has run")
+        if self.pool is not None and self.pool.owner is not self:
+            raise RuntimeError("shared activation pool: another pass ran its forward since this one's - its activations are gone")
+        if not paste_kept and self.prune:
+            raise ValueError("MaePass.reconstruct(paste_kept=False) needs every row predicted: with EngineOptions.prune_dead the decoder computes "
+                             "the scored rows (mask 1) only - build the model with prune_dead=False")
+        La, Lv = cfg.audio_tokens, cfg.video_tokens
+        outs = []
+        for pred, inp, mask, rl, audio, L, xf, pid, base in ((self.p_a, self.audio, self.mask_a, self.rl_a, True, La, self.xf[0], self.pid_a, 0),
+                                                             (self.p_v, self.imgs, self.mask_v, self.rl_v, False, Lv, self.xf[1], self.pid_v, B * La)):
+            want_raw = bool(raw) and xf is not None
+            out, raw_out, err = ops.unpatchify(pred, inp, mask, audio, L, xf=xf, stride=cfg.st, row_id=pid, id_base=base, paste_kept=paste_kept,
+                                               raw=want_raw, row_loss=rl, model_units=not want_raw)
+            outs.append((raw_out if want_raw else out, err))
+        return outs[0][0], outs[1][0].view(self.imgs_shape), outs[0][1], outs[1][1]
 
     def backward(self, gout, reducer=None, accumulate=False):
         cfg, B, T = self.cfg, self.B, self.cfg.frames

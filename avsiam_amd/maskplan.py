@@ -88,6 +88,73 @@ def make_mae_plan(cfg: AVSiamConfig, batch: int, gen: torch.Generator) -> MaePla
     return MaePlan(ka.contiguous(), ra.contiguous(), kv.contiguous(), rv.contiguous())
 
 
+# ---- region plans (CAVMAE_BASE.inpaint): "mask THIS second of audio / THIS corner of the frame" ---------------------------------------------
+def _patch_range(lo, hi, n_patches, stride, what):
+    """patches of `stride` cells that intersect the half-open cell range [lo, hi), clipped to the n_patches the model covers"""
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi <= lo:
+        raise ValueError(f"{what}: [{lo}, {hi}) is not a range (need 0 <= start < end)")
+    p0, p1 = min(lo // stride, n_patches), min(-(-hi // stride), n_patches)
+    if p1 <= p0:
+        raise ValueError(f"{what}: [{lo}, {hi}) lies outside the {n_patches * stride} cells the patches cover")
+    return p0, p1
+
+
+def audio_time_span(cfg: AVSiamConfig, frame0, frame1):
+    """bool [La]: the audio patches that intersect spectrogram frames [frame0, frame1) (all mel bands; token f * audio_t + t)"""
+    t0, t1 = _patch_range(frame0, frame1, cfg.audio_t, cfg.st, "audio_time_span")
+    m = torch.zeros(cfg.audio_f, cfg.audio_t, dtype=torch.bool)
+    m[:, t0:t1] = True
+    return m.reshape(-1)
+
+
+def audio_mel_band(cfg: AVSiamConfig, bin0, bin1):
+    """bool [La]: the audio patches that intersect mel bins [bin0, bin1) (the whole clip)"""
+    f0, f1 = _patch_range(bin0, bin1, cfg.audio_f, cfg.st, "audio_mel_band")
+    m = torch.zeros(cfg.audio_f, cfg.audio_t, dtype=torch.bool)
+    m[f0:f1] = True
+    return m.reshape(-1)
+
+
+def frame_box(cfg: AVSiamConfig, y0, x0, y1, x1):
+    """bool [Lv]: the patches of a frame that intersect rows [y0, y1) x columns [x0, x1) (token gy * grid + gx)"""
+    gy0, gy1 = _patch_range(y0, y1, cfg.grid, cfg.st, "frame_box rows")
+    gx0, gx1 = _patch_range(x0, x1, cfg.grid, cfg.st, "frame_box columns")
+    m = torch.zeros(cfg.grid, cfg.grid, dtype=torch.bool)
+    m[gy0:gy1, gx0:gx1] = True
+    return m.reshape(-1)
+
+
+def make_mae_plan_regions(cfg: AVSiamConfig, batch: int, gen: torch.Generator, must_mask_a=None, must_mask_v=None) -> MaePlan:
+    """make_mae_plan with patches that MUST be removed: bool [B, La] / [B, T, Lv] (or anything that broadcasts to them - the helpers above
+    give one sequence's worth).  The reference's own trick for structured masks (:415-422): the forced tokens' noise is overwritten with 1.1 so
+    that they sort last; the model's keep counts hold (75 % leave, forced ones first, the remainder at random).  Draws the noise make_mae_plan
+    draws: with nothing forced the two give the same plan."""
+    na = torch.rand(batch, cfg.audio_tokens, generator=gen)
+    nv = torch.rand(batch, cfg.frames, cfg.video_tokens, generator=gen)
+    for noise, must, keep, what in ((na, must_mask_a, cfg.keep_a, "audio"), (nv, must_mask_v, cfg.keep_v, "frames")):
+        if must is None:
+            continue
+        must = torch.as_tensor(must)
+        if must.dtype != torch.bool:
+            raise ValueError(f"make_mae_plan_regions: must_mask ({what}) must be bool, got {must.dtype}")
+        try:
+            must = torch.broadcast_to(must, noise.shape)
+        except RuntimeError:
+            raise ValueError(f"make_mae_plan_regions: must_mask ({what}) of shape {tuple(must.shape)} does not broadcast to {tuple(noise.shape)}") from None
+        L = noise.shape[-1]
+        count = must.sum(dim=-1)
+        if int(count.max()) > L - keep:
+            idx = [int(i) for i in torch.nonzero(count > L - keep)[0]]
+            where = f"sample {idx[0]}" + (f", frame {idx[1]}" if len(idx) > 1 else "")
+            raise ValueError(f"make_mae_plan_regions: {what}, {where}: {int(count[tuple(idx)])} patches must be masked but the model removes "
+                             f"{L - keep} of {L} (keeps {keep})")
+        noise[must] = 1.1
+    ka, ra = _unstructured(na, cfg.keep_a)
+    kv, rv = _unstructured(nv, cfg.keep_v)
+    return MaePlan(ka.contiguous(), ra.contiguous(), kv.contiguous(), rv.contiguous())
+
+
 def make_contrastive_plan(cfg: AVSiamConfig, batch: int, gen: torch.Generator, pyrng: _pyrandom.Random) -> ContrastivePlan:
     """Two independent batch permutations chunked into <=5 groups (:533-538); group g masks audio with
     random_masking_structured(ratio 0.2 g, t, f=8, 'tf') (:546, :392-439) and video with

@@ -19,6 +19,7 @@ Differences that are deliberate and documented:
   accumulation across several backward calls are not supported (the reference loop does neither).
 There is no CPU/eager fallback: calling ``forward`` without a GPU and libavsiam_hip.so raises.
 """
+import collections
 import os
 import random as _pyrandom
 
@@ -31,6 +32,9 @@ from ..config import AVSiamConfig, EngineOptions
 from ..maskplan import ContrastivePlan, MaePlan, make_contrastive_plan, make_mae_plan
 from ..param_spec import P1, P2, build_spec
 from ..weights import synth_state
+
+
+Inpainted = collections.namedtuple("Inpainted", "audio imgs mask_a mask_v err_a err_v loss_mae_a loss_mae_v")      # CAVMAE_BASE.inpaint
 
 
 class _Holder(nn.Module):
@@ -448,15 +452,8 @@ class CAVMAE_BASE(nn.Module):
         pc = make_contrastive_plan(self.cfg, batch, gen, pyrng) if contrastive else None
         return pm, pc
 
-    # ---- forward (reference signature, :685) --------------------------------------------------------------------
-    def forward(self, audio, imgs, mask_ratio_a=0.75, mask_ratio_v=0.75, mae_loss_weight=1., contrast_loss_weight=0.01,
-                mask_mode='unstructured', *, mask_plan=None, input_xf=None):
-        """Returns (loss, loss_mae, loss_mae_a, loss_mae_v, loss_c, mask_a, mask_v, c_acc) like the reference (:741).
-        As in the reference, mask_ratio_* and mask_mode are ignored (ratios are fixed at :696 / :546-549) and
-        mae_loss_weight only switches the MAE branch on (:694,739).
-        input_xf (extension, SURVEY.md 8(f) row 4): (ops.InputXf.audio(...), ops.InputXf.frames(...)) - `audio` is then the
-        UN-normalised fbank and `imgs` the uint8 frames as the reference's dataset holds them before its own arithmetic
-        (dataloader.py:505-513, 461-462); the kernels that read the inputs apply it on the fly (either entry may be None)."""
+    def _check_inputs(self, audio, imgs, input_xf):
+        """forward()'s input checks (inpaint() shares them): shapes against the config, the inputs on the device -> (audio, imgs, xf)"""
         self._require_gpu()
         cfg = self.cfg
         B = audio.shape[0]
@@ -474,6 +471,18 @@ class CAVMAE_BASE(nn.Module):
             imgs = imgs.to(self.arena.p.device).contiguous()
         else:
             imgs = imgs.to(self.arena.p.device, torch.float32).contiguous()
+        return audio, imgs, xf
+
+    # ---- forward (reference signature, :685) --------------------------------------------------------------------
+    def forward(self, audio, imgs, mask_ratio_a=0.75, mask_ratio_v=0.75, mae_loss_weight=1., contrast_loss_weight=0.01,
+                mask_mode='unstructured', *, mask_plan=None, input_xf=None):
+        """Returns (loss, loss_mae, loss_mae_a, loss_mae_v, loss_c, mask_a, mask_v, c_acc) like the reference (:741).
+        As in the reference, mask_ratio_* and mask_mode are ignored (ratios are fixed at :696 / :546-549) and
+        mae_loss_weight only switches the MAE branch on (:694,739).
+        input_xf (extension, SURVEY.md 8(f) row 4): (ops.InputXf.audio(...), ops.InputXf.frames(...)) - `audio` is then the
+        UN-normalised fbank and `imgs` the uint8 frames as the reference's dataset holds them before its own arithmetic
+        (dataloader.py:505-513, 461-462); the kernels that read the inputs apply it on the fly (either entry may be None)."""
+        audio, imgs, xf = self._check_inputs(audio, imgs, input_xf)
         do_m, do_c = mae_loss_weight != 0, contrast_loss_weight != 0
         if self.share_pass_buffers and do_m and do_c and torch.is_grad_enabled():
             raise RuntimeError("share_pass_buffers: the two passes use the same activation memory, so a combined-loss forward with gradients "
@@ -503,6 +512,38 @@ class CAVMAE_BASE(nn.Module):
         mask_a, mask_v = (masks[0], masks[1]) if (do_m and not do_c) else (None, None)     # :594 - the mixed encoder returns None
         loss = loss_c + loss_mae                                                          # :739
         return loss, loss_mae, la, lv, loss_c, mask_a, mask_v, c_acc
+
+    # ---- reconstructions (unpatchify, :353-363; norm_pix_loss stays off at :672 so that they mean something) ---------------------------
+    def inpaint(self, audio, imgs, *, mask_plan=None, input_xf=None, paste_kept=True, raw=False):
+        """What the masked autoencoder fills in: one MAE pass under no_grad (whatever the caller's grad mode), then the decoder's predictions
+        put back into pictures on the device (csrc/inpaint.hip) -> Inpainted(audio [B, T, F], imgs (shape of the input), mask_a, mask_v,
+        err_a [B, La], err_v [B, T * Lv], loss_mae_a, loss_mae_v), all device tensors.
+        mask_plan: a MaePlan - maskplan.make_mae_plan_regions masks chosen spans of time, mel bands or boxes of the frames - or None for a
+        plan drawn on the device (from a key stream of its own: the training plans that follow are the ones they would have been).
+        input_xf: as forward().  paste_kept: kept patches are the input as the model saw it, bit for bit; False: every patch is the
+        decoder's (needs EngineOptions.prune_dead off).  raw: outputs in the units of the raw inputs (un-normalised fbank; uint8 frames) -
+        only with input_xf, and not with the noise augmentation (shift / amp).
+        The call is a forward of the MAE pass: a pending MAE forward of the same batch size cannot be backpropagated afterwards.  In the fp8
+        modes it advances the delayed-scaling records like any forward."""
+        if mask_plan is not None and not isinstance(mask_plan, MaePlan):
+            raise TypeError("inpaint: mask_plan must be a MaePlan (maskplan.make_mae_plan / make_mae_plan_regions) or None")
+        if raw and input_xf is None:
+            raise ValueError("inpaint: raw=True returns the inputs' own units, so it needs the input_xf the raw inputs came with")
+        audio, imgs, xf = self._check_inputs(audio, imgs, input_xf)
+        if raw and xf[0] is not None and xf[0].shift:
+            raise ValueError("inpaint: raw=True is refused with the noise augmentation (shift / amp): a rolled, noised spectrogram has no original units")
+        self.flush_deferred()
+        self._sync_shadows()
+        with torch.no_grad():
+            eng = self._engine("mae", audio.shape[0])
+            if mask_plan is None:
+                self._rngs()
+                self._inpaint_draws = getattr(self, "_inpaint_draws", 0) + 1
+                # (the upper half of the counter space: _next_seed's counts - the training plans - are neither used nor advanced)
+                eng.draw_device(((self._seed_base & 0xFFFFFFFF) << 32) | 0x80000000 | (self._inpaint_draws & 0x7FFFFFFF), self._np_rng())
+            _, la, lv, ma, mv = eng.forward(audio, imgs, mask_plan, xf)
+            ra, rv, ea, ev = eng.reconstruct(paste_kept=paste_kept, raw=raw)
+            return Inpainted(ra, rv, ma.clone(), mv.clone(), ea, ev, la.clone().reshape(()), lv.clone().reshape(()))
 
     # ---- fused data-parallel + optimizer step over the flat arena -------------------------------------------------
     def allreduce_grads(self, which, average=True, already_reduced=None):

@@ -977,6 +977,50 @@ def mae_loss_bwd(pred, inp, mask, gout, dpred, audio, L, nmask, xf=None, stride=
               _xf_arg(xf, 1 if audio else 2, inp.shape[0] if audio else None), row_id, int(id_base), _stream())
 
 
+def unpatchify(pred, inp, mask, audio, L, xf=None, stride=16, row_id=None, id_base=0, paste_kept=True, raw=False, row_loss=None, out=None, raw_out=None, err=None,
+               model_units=True):
+    """The way back from prediction rows (include/avsiam_hip.h: avs_unpatchify): -> (out, raw_out, err).  out: fp32 in the shape of ``inp``, the
+    scored patches (mask 1; paste_kept False: every patch that has a row) from ``pred``, everything else ``inp`` through ``xf``.  raw: also the
+    picture in the input's own units (audio fp32, frames uint8; needs xf without shift / amp), else raw_out is None.  row_loss: also the
+    per-token error map err [mask.shape], else None.  out / raw_out / err: buffers to write into (the tests' guard bands); None allocates.
+    model_units False (with raw): only the raw picture is wanted, out is None."""
+    _chk(row_id, I32, "unp.row_id")
+    _chk(pred, F32, "unp.pred", 2); _chk(inp, U8 if (xf is not None and not audio) else F32, "unp.inp"); _chk(mask, F32, "unp.mask"); _chk(row_loss, F32, "unp.row_loss")
+    _chk(out, F32, "unp.out"); _chk(raw_out, F32 if audio else U8, "unp.raw_out"); _chk(err, F32, "unp.err")
+    npos = mask.numel()
+    if audio:
+        C, H, W = 1, inp.shape[1], inp.shape[2]          # [B, time, mel]
+        assert inp.dim() == 3
+    else:
+        assert inp.dim() >= 3
+        C, H, W = inp.shape[-3:]
+    n = inp.numel() // (C * H * W)
+    assert npos == n * L and pred.shape[1] == 256 * C and (H // stride) * (W // stride) == L and 0 < stride <= 16
+    prows = npos if row_id is None else row_id.numel()
+    assert pred.shape[0] >= prows and (row_loss is None or row_loss.numel() >= prows)
+    if raw:
+        if xf is None:
+            raise _lib.AvsiamHipError("unpatchify: raw=True needs the input transform it inverts (xf)")
+        if xf.shift:
+            raise _lib.AvsiamHipError("unpatchify: raw=True is refused with a per-sample shift / amp: a rolled, noised input has no original units")
+    elif raw_out is not None:
+        raise _lib.AvsiamHipError("unpatchify: raw_out given without raw=True")
+    if err is not None and row_loss is None:
+        raise _lib.AvsiamHipError("unpatchify: err given without row_loss")
+    dev = pred.device
+    if out is None and (model_units or not raw):
+        out = torch.empty(inp.shape, dtype=F32, device=dev)
+    if raw and raw_out is None:
+        raw_out = torch.empty(inp.shape, dtype=F32 if audio else U8, device=dev)
+    if row_loss is not None and err is None:
+        err = torch.empty(mask.shape, dtype=F32, device=dev)
+    assert (out is None or out.numel() >= inp.numel()) and (raw_out is None or raw_out.numel() >= inp.numel()) and (err is None or err.numel() >= npos)
+    inv = torch.empty(npos, dtype=I32, device=dev) if row_id is not None else None
+    _call("avs_unpatchify", pred, inp, mask, out, raw_out, row_loss, err, prows, int(audio), n, L, C, H, W, int(stride),
+          _xf_arg(xf, 1 if audio else 2, inp.shape[0] if audio else None), row_id, int(id_base), inv, int(bool(paste_kept)), _stream())
+    return out, raw_out, err
+
+
 def l2norm_fwd(x, xn, norm):
     _chk(x, F32, "l2.x", 2); _chk(xn, F32, "l2.xn", 2); _chk(norm, F32, "l2.norm")
     assert xn.shape == x.shape and norm.numel() >= x.shape[0]

@@ -314,3 +314,49 @@ def normalize_frames(frames_u8, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT
     _lib.call("avs_normalize_frames_u8", frames_u8, out, n, plane, ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p),
               _lib.current_stream())
     return out
+
+
+def unpatchify_reference(rows, base, audio, stride=16, mask=None):
+    """numpy restatement of avs_unpatchify (unpatchify, cav_mae_base.py:353-363, on 16 x 16 patch storage): rows [n, L, 256 * C] -> a copy of
+    ``base`` ([n, T, F] spectrograms, or [n, C, H, W] frames) with the stride x stride cells of every token (``mask`` [n, L] given: of the
+    tokens whose mask is 1) taken from its row.  Audio: token f * tP + t, element p * 16 + q -> cell (t * S + q, f * S + p); frames: token
+    gy * G + gx, element (p * 16 + q) * C + c -> cell (c, gy * S + p, gx * S + q).  Cells no patch covers keep ``base``.  Pure data movement:
+    the result holds the rows' and the base's values bit for bit."""
+    rows, out = np.asarray(rows), np.array(base, copy=True)
+    S = int(stride)
+    if audio:
+        n, T, F = out.shape
+        C, nr, nc = 1, T // S, F // S                                       # time patches, mel patches
+    else:
+        n, C, H, W = out.shape
+        nr, nc = H // S, W // S
+    L = nr * nc
+    if rows.shape != (n, L, 256 * C) or not 0 < S <= 16:
+        raise ValueError(f"unpatchify_reference: rows {rows.shape} for {n} pictures of {L} tokens x {256 * C}, stride {S}")
+    take = np.ones((n, L), dtype=bool) if mask is None else np.asarray(mask).reshape(n, L) == 1
+    if audio:
+        r = rows.reshape(n, nc, nr, 16, 16)[:, :, :, :S, :S]                # [n, f, t, p, q]
+        full = r.transpose(0, 2, 4, 1, 3).reshape(n, nr * S, nc * S)        # [n, t, q, f, p]
+        tk = take.reshape(n, nc, nr).transpose(0, 2, 1)                     # [n, t, f]
+        tk = np.repeat(np.repeat(tk, S, axis=1), S, axis=2)
+        view = out[:, :nr * S, :nc * S]
+    else:
+        r = rows.reshape(n, nr, nc, 16, 16, C)[:, :, :, :S, :S]             # [n, gy, gx, p, q, c]
+        full = r.transpose(0, 5, 1, 3, 2, 4).reshape(n, C, nr * S, nc * S)  # [n, c, gy, p, gx, q]
+        tk = np.repeat(np.repeat(take.reshape(n, 1, nr, nc), S, axis=2), S, axis=3)
+        tk = np.broadcast_to(tk, full.shape)
+        view = out[:, :, :nr * S, :nc * S]
+    view[tk] = full[tk]
+    return out
+
+
+def unnormalize_reference(x, mean, std, audio):
+    """numpy float32 restatement of avs_unpatchify's raw output: audio x * std + mean; frames [..., 3, H, W] -> uint8
+    rint((x * std_c + mean_c) * 255) clamped to 0..255.  Multiply and add are rounded separately, as the kernel does."""
+    x = np.asarray(x, dtype=np.float32)
+    if audio:
+        return x * np.float32(std) + np.float32(mean)
+    shape = (3, 1, 1)
+    v = (x * np.asarray(std, dtype=np.float32).reshape(shape) + np.asarray(mean, dtype=np.float32).reshape(shape)) * np.float32(255.0)
+    with np.errstate(invalid="ignore"):
+        return np.clip(np.nan_to_num(np.rint(v), nan=0.0), 0, 255).astype(np.uint8)

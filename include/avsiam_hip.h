@@ -419,6 +419,20 @@ int avs_mae_loss_fwd_id(const float* pred, const void* inp, const float* mask, f
 int avs_mae_loss_bwd_id(const float* pred, const void* inp, const float* mask, const float* gout, avs_bf16* dpred, int rows, int audio,
                         int L, int C, int H, int W, float nmask, int stride, const avs_input_xf* xf, const int* row_id, int id_base,
                         avs_stream_t stream);
+/* ---- the way back (unpatchify, cav_mae_base.py:353-363): prediction rows -> the picture the model was shown, the inverse of the index
+ * arithmetic above.  n pictures of L = (H / stride) * (W / stride) tokens; audio: [n, H = time, W = mel], C = 1, token f * (H / stride) + t;
+ * frames: [n, C, H, W], token gy * (W / stride) + gx.  A cell takes pred[pr, e] where mask[n * L + l] == 1 (paste_kept 0: wherever its
+ * token has a prediction row), else the input through `xf` - bit for bit what the loss read as its target; cells no patch covers take the
+ * input.  pr = n * L + l (row_id NULL; rows == n * L) or the row with row_id[pr] - id_base == n * L + l (compact rows; inv_ws: n * L int32
+ * of workspace the call overwrites; a token without a row takes the input).  Outputs, each may be NULL (not all three):
+ *   out      fp32, shape of the input, in the model's units
+ *   raw_out  the same through the inverse of xf, multiply and add rounded separately: audio fp32 x * std + mean; frames uint8
+ *            rint((x * std_c + mean_c) * 255) clamped to 0..255.  Needs xf; refused (-2) when xf carries shift / amp
+ *   err      fp32 [n * L]: row_loss[pr] (what avs_mae_loss_fwd_id wrote) where mask == 1, else 0
+ * pred must be 16-byte aligned; C <= 3.  One writer per cell, no atomics: the same bytes every call. */
+int avs_unpatchify(const float* pred, const void* inp, const float* mask, float* out, void* raw_out, const float* row_loss, float* err,
+                   int rows, int audio, int n, int L, int C, int H, int W, int stride, const avs_input_xf* xf, const int* row_id,
+                   int id_base, int* inv_ws, int paste_kept, avs_stream_t stream);
 
 /* ---- fine-tuning augmentation where the input is read (dataloader_ft.py:527-548, training set only, per sample, in this order):
  * FrequencyMasking(freqm) and TimeMasking(timem) on the un-normalised fbank (mask value 0.0; each skipped when its parameter is 0), then
