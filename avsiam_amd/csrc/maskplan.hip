@@ -19,6 +19,9 @@
 //   pos_row[dec row]               = pos_base + token              which row of the positional table [pos_a ; pos_v] the row's token takes
 //   row_of_pos[dec_off + token]    = dec row                       the inverse (un-shuffle backward walks the positions)
 //   pred_id[pred_off + j - keep]   = mask_off + token              which (sample, token) a compact prediction row scores
+// RESTATEMENT: maskplan.plan_reference (numpy, a stable argsort instead of the network) writes the same elements from the contract above;
+// tests/test_maskplan_gpu.py holds this kernel to it bit for bit, tests/test_maskplan_cpu.py holds it to the reference's law, and
+// tests/golden/plan_stream_v1.npz pins the stream: a change of the draw has to change all three on purpose.
 #include "common.h"
 
 struct PlanSeq {        // one sequence to draw (int32 x 16, filled by the host)

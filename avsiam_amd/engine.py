@@ -27,7 +27,7 @@ import torch
 from . import ops
 from .arena import ParamArena
 from .config import AVSiamConfig, EngineOptions
-from .maskplan import ContrastivePlan, MaePlan, group_sizes, group_ratio, len_keep
+from .maskplan import ContrastivePlan, MaePlan, draw_structured, group_sizes, group_ratio, len_keep
 
 BF16, F32, I32, U8 = torch.bfloat16, torch.float32, torch.int32, torch.uint8
 LN_EPS_BLOCK, LN_EPS_FINAL = 1e-5, 1e-6       # nn.LayerNorm default in Block; timm ViT final norm
@@ -909,29 +909,14 @@ class ContrastivePass:
                       ids_out=self.ids_dev, seed_dev=seed_dev)
 
     def draw_host(self, nprng):
-        cfg, B, T = self.cfg, self.B, self.cfg.frames
-        t, f = cfg.audio_t, cfg.audio_f
-        perm_a, perm_v = nprng.permutation(B), nprng.permutation(B)
+        B, T = self.B, self.cfg.frames
+        perm_a, perm_v, bits, tmask_x = draw_structured(self.cfg, self.slot_group, nprng)      # (the numpy part: maskplan.py)
         d = self.desc_host
         d[:B, 3] = perm_a
         d[B:, 3] = (perm_v[:, None] * T + np.arange(T)[None, :]).reshape(-1)
-        ratios = np.array([group_ratio(int(g)) for g in self.slot_group])
-        nt = np.array([int(t * r * 0.7) for r in ratios])
-        nf = np.array([int(f * r * 0.7) for r in ratios])
-        # random.sample(range(t), n): the n smallest of t random keys
-        rank_t = np.argsort(np.argsort(nprng.random((B, t)), axis=1), axis=1)
-        rank_f = np.argsort(np.argsort(nprng.random((B, f)), axis=1), axis=1)
-        assert t <= 96 and f <= 32, "structured masks are bit sets: at most 96 time and 32 frequency patches"
-        tm = (rank_t < nt[:, None]).astype(np.uint64)
-        fm = (rank_f < nf[:, None]).astype(np.uint64)
-        tbits = (tm[:, :64] << np.arange(min(t, 64), dtype=np.uint64)[None, :]).sum(axis=1)
-        fbits = (fm << np.arange(f, dtype=np.uint64)[None, :]).sum(axis=1)
         self.bits_host[:] = 0
-        self.bits_host[0, :B] = (tbits & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
-        self.bits_host[1, :B] = (tbits >> np.uint64(32)).astype(np.uint32).view(np.int32)
-        self.bits_host[2, :B] = fbits.astype(np.uint32).view(np.int32)
-        if t > 64:                                               # time patches 64.. travel in the descriptor (PlanSeq.tmask_x)
-            d[:B, 9] = (tm[:, 64:] << np.arange(t - 64, dtype=np.uint64)[None, :]).sum(axis=1).astype(np.uint32).view(np.int32)
+        self.bits_host[:, :B] = bits
+        d[:B, 9] = tmask_x                                       # time patches 64.. travel in the descriptor (PlanSeq.tmask_x)
         self.desc_dev.copy_(torch.from_numpy(d), non_blocking=True)
         self.bits_dev.copy_(torch.from_numpy(self.bits_host), non_blocking=True)
         self._set_slot_maps(np.concatenate([perm_a, B + perm_v]))

@@ -18,6 +18,7 @@ import random as _pyrandom
 from dataclasses import dataclass
 from typing import List
 
+import numpy as np
 import torch
 
 from .config import AVSiamConfig
@@ -218,3 +219,115 @@ def plan_from_arrays(d):
     a_keep = [d["a_keep"][b][d["a_keep"][b] >= 0].long() for b in range(B)]
     v_keep = [[d["v_keep"][b, t][d["v_keep"][b, t] >= 0].long() for t in range(T)] for b in range(B)]
     return ContrastivePlan(d["a_group"].long(), d["v_group"].long(), a_keep, v_keep)
+
+
+# ---- the device draw, restated on the host (numpy; tests/test_maskplan_*.py hold csrc/maskplan.hip to this) -------------------------------------
+PLAN_OUTPUTS = ("row_src", "row_tok", "src_row", "mask", "ids", "pos_row", "row_of_pos", "pred_id")
+
+
+def plan_noise(L, sq, seed):
+    """float32 [L]: the noise of tokens 0..L-1 of sequence number `sq` of a launch under the 64-bit key `seed` - word 0 of
+    Philox4x32-10 with counter (token, sq, 0, 0) and key (seed low, seed high), its top 24 bits scaled into [0, 1) (like torch.rand)."""
+    from .preprocess import philox4x32_10
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10(np.arange(L, dtype=np.uint64), int(sq), 0, 0, seed & 0xFFFFFFFF, seed >> 32)
+    return (w >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def plan_forced(L, t_patches, tmask_lo, tmask_hi, tmask_x, fmask):
+    """bool [L]: the tokens of an [f][t_patches] grid (token = f * t_patches + t) that structured masking forces out: time column t is in
+    the 96-bit set tmask_lo | tmask_hi << 32 | tmask_x << 64, or frequency row f in the 32-bit set fmask.  The words are taken as unsigned
+    (an int32 with bit 31 set is negative); bits at or above t_patches / the number of rows name nothing."""
+    m = 0xFFFFFFFF
+    tbits = (int(tmask_lo) & m) | ((int(tmask_hi) & m) << 32) | ((int(tmask_x) & m) << 64)
+    fbits = int(fmask) & m
+    rows = -(-L // t_patches)
+    col = np.array([(tbits >> c) & 1 for c in range(t_patches)], dtype=bool)
+    row = np.array([(fbits >> r) & 1 for r in range(rows)], dtype=bool)
+    i = np.arange(L)
+    return col[i % t_patches] | row[i // t_patches]
+
+
+def plan_shuffle(desc_row, sq, seed, tmask_lo=None, tmask_hi=None, fmask=None):
+    """int64 [L]: the shuffle of sequence `sq` (its descriptor: desc_row) - tokens by ascending noise, equal noise by ascending index"""
+    L, t_p = int(desc_row[0]), int(desc_row[6])
+    noise = plan_noise(L, sq, seed)
+    if t_p > 0:
+        noise[plan_forced(L, t_p, tmask_lo[sq], tmask_hi[sq], desc_row[9], fmask[sq])] = np.float32(1.1)    # "large value will be removed"
+    return np.argsort(noise, kind="stable")
+
+
+def plan_reference(desc, seed, tmask_lo=None, tmask_hi=None, fmask=None, out=None):
+    """What one launch of the mask-plan kernel (csrc/maskplan.hip, ops.mask_plan) writes, restated from its contract with numpy alone.
+    desc: int32 [nseq, 16] descriptors (0 L, 1 keep, 2 row_off, 3 src_id, 4 dec_off, 5 enc_base, 6 t_patches, 7 ids_off, 8 mask_off,
+    9 tmask_x, 12 dec_m_off, 13 dec_k_off, 14 pred_off, 15 pos_base); seed: the 64-bit Philox key; tmask_lo / tmask_hi / fmask: the per-sequence
+    bit sets of the structured sequences (read at the sequence's index, only where t_patches > 0).
+    out: dict of numpy arrays named as PLAN_OUTPUTS (those a launch does not need may be missing); exactly the elements the kernel writes
+    are written, every other element is left alone - pre-fill with a sentinel to see that.  -> out.
+
+    With j the rank of token `tok` in the sequence's shuffle (plan_shuffle: stable ascending order of the noise, forced tokens at 1.1):
+      row_src / row_tok[row_off + j] = src_id / tok                 j < keep
+      ids[ids_off + j]               = tok                          ids_off >= 0
+    and for dec_off >= 0
+      mask[mask_off + tok]           = 0 kept | 1 removed
+      classic (dec_m_off < 0):  src_row[dec_off + tok] = enc_base + j | -1
+      grouped:                  row r = dec_k_off + j (kept) | dec_m_off + j - keep (removed);  src_row[r] = enc_base + j | -1;
+                                pos_row[r] = pos_base + tok;  row_of_pos[dec_off + tok] = r;  pred_id[pred_off + j - keep] = mask_off + tok"""
+    desc = np.asarray(desc)
+    assert desc.ndim == 2 and desc.shape[1] == 16
+    if out is None:
+        out = {}
+    for sq in range(desc.shape[0]):
+        L, keep, row_off, src_id, dec_off, enc_base, _, ids_off, mask_off, _, _, _, dec_m, dec_k, pred_off, pos_base = (int(x) for x in desc[sq])
+        tok = plan_shuffle(desc[sq], sq, seed, tmask_lo, tmask_hi, fmask)
+        j = np.arange(L)
+        kept = j < keep
+        out["row_src"][row_off:row_off + keep] = src_id
+        out["row_tok"][row_off:row_off + keep] = tok[:keep]
+        if ids_off >= 0:
+            out["ids"][ids_off:ids_off + L] = tok
+        if dec_off < 0:
+            continue
+        src = np.where(kept, enc_base + j, -1)
+        out["mask"][mask_off + tok] = np.where(kept, 0.0, 1.0)
+        if dec_m < 0:
+            out["src_row"][dec_off + tok] = src
+        else:
+            r = np.where(kept, dec_k + j, dec_m + j - keep)
+            out["src_row"][r] = src
+            out["pos_row"][r] = pos_base + tok
+            out["row_of_pos"][dec_off + tok] = r
+            out["pred_id"][pred_off + j[keep:] - keep] = mask_off + tok[keep:]
+    return out
+
+
+def draw_structured(cfg: AVSiamConfig, slot_group, nprng):
+    """The host part of the contrastive pass's device draw: what forward_encoder_mmixed draws outside random_masking_* (two randperm +
+    chunk, cav_mae_base.py:533-538) and the time-column / frequency-row picks of random_masking_structured mode 'tf' (:415-422).
+    slot_group[sl]: the multi-ratio group of slot sl (group-major); nprng: a numpy Generator, advanced by permutation(B) twice, then
+    random((B, t)) and random((B, f)).  -> (perm_a, perm_v, bits int32 [3, B], tmask_x int32 [B]): slot sl holds audio sample perm_a[sl]
+    and video sample perm_v[sl]; its int(t * r * 0.7) time columns are the set bits[0] | bits[1] << 32 | tmask_x << 64 (words taken
+    as unsigned), its int(f * r * 0.7) frequency rows the set bits[2]."""
+    slot_group = np.asarray(slot_group)
+    B = slot_group.shape[0]
+    t, f = cfg.audio_t, cfg.audio_f
+    perm_a, perm_v = nprng.permutation(B), nprng.permutation(B)
+    ratios = np.array([group_ratio(int(g)) for g in slot_group])
+    nt = np.array([int(t * r * 0.7) for r in ratios])
+    nf = np.array([int(f * r * 0.7) for r in ratios])
+    # random.sample(range(t), n): the n smallest of t random keys
+    rank_t = np.argsort(np.argsort(nprng.random((B, t)), axis=1), axis=1)
+    rank_f = np.argsort(np.argsort(nprng.random((B, f)), axis=1), axis=1)
+    assert t <= 96 and f <= 32, "structured masks are bit sets: at most 96 time and 32 frequency patches"
+    tm = (rank_t < nt[:, None]).astype(np.uint64)
+    fm = (rank_f < nf[:, None]).astype(np.uint64)
+    tbits = (tm[:, :64] << np.arange(min(t, 64), dtype=np.uint64)[None, :]).sum(axis=1)
+    fbits = (fm << np.arange(f, dtype=np.uint64)[None, :]).sum(axis=1)
+    bits = np.zeros((3, B), dtype=np.int32)
+    bits[0] = (tbits & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+    bits[1] = (tbits >> np.uint64(32)).astype(np.uint32).view(np.int32)
+    bits[2] = fbits.astype(np.uint32).view(np.int32)
+    tmask_x = np.zeros(B, dtype=np.int32)
+    if t > 64:                                               # time patches 64.. travel in the descriptor (PlanSeq.tmask_x)
+        tmask_x[:] = (tm[:, 64:] << np.arange(t - 64, dtype=np.uint64)[None, :]).sum(axis=1).astype(np.uint32).view(np.int32)
+    return perm_a, perm_v, bits, tmask_x
