@@ -1531,3 +1531,102 @@ def resize_frames(v_u8, sizes=None, *, partner=None, partner_sizes=None, weight=
     _launch("resize_frames", (0.0, nbytes), "avs_resize_frames_u8", v_u8, Hs, Ws, sizes, mh, mw, partner, Hs2, Ws2, partner_sizes, mh2, mw2, weight, out, n,
             n // B, out_h, out_w, ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p), _stream())
     return out
+
+
+# ---- source-rate audio (fine-tuning loader: dataloader_ft.py:272-277, 298-306) -----------------------------------------------------------
+RESAMPLE_MAX_RATES, RESAMPLE_MAX_CHANNELS, RESAMPLE_MAX_WORDS, RESAMPLE_MAX_SPAN, RESAMPLE_TILE = 8, 8, 16384, 16384, 1024      # csrc/resample.hip
+_resample_tables = {}         # (orig, new, device) -> (device table, (o, n, width, taps))
+_resample_index = {}          # (per-clip table indices, device) -> int32 device tensor
+
+
+def resample_table(orig_freq, new_freq, device):
+    """The compact filter bank of one rate pair on `device`, built once from preprocess.resample_table_reference (torch on the CPU: the
+    kernel's weights are that table's bits) and kept: -> (fp32 device tensor of n + n * pitch words: int32 first[n], then w[n][pitch], pitch =
+    taps | 1; (o, n, width, taps)).  A rate pair whose compact table or whose tile span is over the kernel's caps is refused before the
+    dense table is built."""
+    import math
+    import numpy as np
+    from . import preprocess
+    device = torch.device(device)
+    key = (int(orig_freq), int(new_freq), device)
+    hit = _resample_tables.get(key)
+    if hit is not None:
+        return hit
+    o, n = preprocess._resample_ratio(orig_freq, new_freq)
+    width = math.ceil(6 * o / (min(o, n) * 0.99))
+    if n * 14 > RESAMPLE_MAX_WORDS:                                     # a phase has at least 12 taps: 2 * 6 zero crossings
+        raise _lib.AvsiamHipError(f"resample_wave: {orig_freq} -> {new_freq} Hz has {n} phases: compact tables above {RESAMPLE_MAX_WORDS} words are refused")
+    if ((RESAMPLE_TILE - 1) // n + 2) * o + 2 * width + 3 > RESAMPLE_MAX_SPAN:
+        raise _lib.AvsiamHipError(f"resample_wave: {orig_freq} -> {new_freq} Hz: the input span of {RESAMPLE_TILE} outputs is over {RESAMPLE_MAX_SPAN} samples")
+    table, width = preprocess.resample_table_reference(orig_freq, new_freq)
+    first, weights = preprocess.resample_compact_table(table)
+    taps = weights.shape[1]
+    pitch = taps | 1
+    if n * (pitch + 1) > RESAMPLE_MAX_WORDS:
+        raise _lib.AvsiamHipError(f"resample_wave: {orig_freq} -> {new_freq} Hz: {n} phases x {taps} taps: compact tables above {RESAMPLE_MAX_WORDS} words are refused")
+    block = np.zeros(n + n * pitch, dtype=np.float32)
+    block[:n] = first.view(np.float32)
+    block[n:].reshape(n, pitch)[:, :taps] = weights
+    hit = (torch.from_numpy(block).to(device), (o, n, int(width), taps))
+    _resample_tables[key] = hit
+    return hit
+
+
+def resample_wave(wave, rates, lengths=None, *, new_freq=16000, out=None, out_lengths=None):
+    """Decoded PCM at the files' own rates to mono audio at `new_freq` in one launch (avs_resample_wave, csrc/resample.hip; the specification is
+    preprocess.resample_reference): torchaudio.functional.resample(waveform, sr, new_freq) - windowed sinc, sinc_interp_hann, width 6, rolloff
+    0.99 - when sr != new_freq, and waveform.mean(dim=0) (dataloader_ft.py:272-277, 298-306).
+
+    wave fp32 [B, stride] or [B, C, stride], 1 <= C <= 8.  rates: a HOST int or B host ints, each clip's own rate (the loader knows it from the
+    file header); at most 8 distinct rates other than new_freq per call.  lengths: samples per clip, None = stride; host values are checked
+    (0 .. stride, ValueError) and uploaded, an int32 device tensor is taken at its word and cut to 0 .. stride on the device.
+    -> (out fp32 [B, out_stride], out_lengths int32 [B] on the device): out_lengths[b] = ceil(n len / o) in exact integers, the row is zero from
+    there; out_stride is the largest ceil(n stride / o) over the call's rates; `out` / `out_lengths` given: written in place.  A clip at new_freq is not filtered: its channel mean (C = 1:
+    its bytes).  One launch (plus a table upload on a rate's first use), no host synchronisation, no atomics: two calls give identical bytes."""
+    from . import preprocess
+    _chk(wave, F32, "resample_wave.wave")
+    if wave.dim() not in (2, 3):
+        raise _lib.AvsiamHipError(f"resample_wave: need fp32 [B, stride] or [B, C, stride], got {tuple(wave.shape)}")
+    B, stride = wave.shape[0], wave.shape[-1]
+    C = wave.shape[1] if wave.dim() == 3 else 1
+    dev = wave.device
+    if B < 1 or stride < 1 or C < 1:
+        raise _lib.AvsiamHipError(f"resample_wave: wave {tuple(wave.shape)}: need at least one clip, one channel and one sample")
+    if C > RESAMPLE_MAX_CHANNELS:
+        raise _lib.AvsiamHipError(f"resample_wave: {C} channels: at most {RESAMPLE_MAX_CHANNELS}")
+    if isinstance(rates, (str, bytes)):
+        raise ValueError(f"resample_wave: rates {rates!r}: a host int or {B} host ints")
+    rates = [rates] * B if not hasattr(rates, "__len__") else list(rates)
+    if len(rates) != B:
+        raise _lib.AvsiamHipError(f"resample_wave: {len(rates)} rates for {B} clips")
+    ratios = [preprocess._resample_ratio(r, new_freq) for r in rates]                      # ValueError: not positive integers
+    new_freq = int(new_freq)
+    distinct = sorted({int(r) for r in rates if int(r) != new_freq})
+    if len(distinct) > RESAMPLE_MAX_RATES:
+        raise _lib.AvsiamHipError(f"resample_wave: {len(distinct)} distinct rates in one call: at most {RESAMPLE_MAX_RATES}")
+    tabs = [resample_table(r, new_freq, dev) for r in distinct]
+    idx = tuple(distinct.index(int(r)) if int(r) != new_freq else -1 for r in rates)
+    tab_idx = _resample_index.get((idx, dev))
+    if tab_idx is None:
+        if len(_resample_index) >= 256:
+            _resample_index.clear()
+        tab_idx = _resample_index[(idx, dev)] = torch.tensor(idx, dtype=I32).to(dev)
+    out_stride = max(-((-n * stride) // o) for o, n in ratios)
+    lengths = _per_clip(lengths, B, I32, "resample_wave.lengths", dev, 0, stride)
+    if out is None:
+        out = torch.empty((B, out_stride), dtype=F32, device=dev)
+    else:
+        _chk(out, F32, "resample_wave.out", 2)
+        if tuple(out.shape) != (B, out_stride) or out.device != dev:
+            raise _lib.AvsiamHipError(f"resample_wave.out: expected {(B, out_stride)} on {dev}, got {tuple(out.shape)} on {out.device}")
+    if out_lengths is None:
+        out_lengths = torch.empty(B, dtype=I32, device=dev)
+    else:
+        _chk(out_lengths, I32, "resample_wave.out_lengths", 1)
+        if out_lengths.numel() != B or out_lengths.device != dev:
+            raise _lib.AvsiamHipError(f"resample_wave.out_lengths: expected {B} values on {dev}, got {tuple(out_lengths.shape)} on {out_lengths.device}")
+    ptrs = (ctypes.c_void_p * max(1, len(tabs)))(*[t.data_ptr() for t, _ in tabs])
+    geo = (ctypes.c_int * max(4, 4 * len(tabs)))(*[v for _, g in tabs for v in g])
+    _launch("resample_wave", (0.0, 4.0 * (wave.numel() + out.numel())), "avs_resample_wave", wave, B, C, stride, lengths, tab_idx, len(tabs),
+            ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(geo, ctypes.c_void_p), out, out_stride, out_lengths, _stream())
+    return out, out_lengths

@@ -360,3 +360,159 @@ def unnormalize_reference(x, mean, std, audio):
     v = (x * np.asarray(std, dtype=np.float32).reshape(shape) + np.asarray(mean, dtype=np.float32).reshape(shape)) * np.float32(255.0)
     with np.errstate(invalid="ignore"):
         return np.clip(np.nan_to_num(np.rint(v), nan=0.0), 0, 255).astype(np.uint8)
+
+
+# ---- source-rate audio: the windowed-sinc resample of the fine-tuning loader (dataloader_ft.py:272-277, 298-306) ---------------------------
+RESAMPLE_MAX_RATES, RESAMPLE_MAX_CHANNELS, RESAMPLE_MAX_WORDS = 8, 8, 16384
+
+
+def _resample_ratio(orig_freq, new_freq):
+    """(o, n): the two rates over their gcd; ValueError for anything but positive integers"""
+    import math
+    import numbers
+    for f in (orig_freq, new_freq):
+        if isinstance(f, bool) or not isinstance(f, numbers.Integral) or int(f) < 1:
+            raise ValueError(f"resample: rates must be positive integers, got {orig_freq!r} -> {new_freq!r}")
+    g = math.gcd(int(orig_freq), int(new_freq))
+    return int(orig_freq) // g, int(new_freq) // g
+
+
+def _resample_phase(n):
+    """the phase term of the table, -p / n for p = 0 .. n - 1 as torch promotes it: an int64 arange divided by an int is FLOAT32"""
+    return torch.arange(0, -n, -1)[:, None, None] / n
+
+
+def resample_table_reference(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """The filter bank of torchaudio.functional.resample(waveform, orig_freq, new_freq) - torchaudio's _get_sinc_resample_kernel with
+    resampling_method='sinc_interp_hann' and dtype=None, as functional.resample calls it - restated in torch on the CPU so that torch's own
+    type promotion decides the dtypes.  The formula is written down from the maintainer's memory of torchaudio: torchaudio was not available
+    where this was written, NO RECORDING EXISTS TO CHECK IT AGAINST, and someone with torchaudio can add a golden under tests/golden/.
+
+      g = gcd(orig, new); o = orig // g; n = new // g
+      base  = min(o, n) * rolloff
+      width = ceil(lowpass_filter_width * o / base)
+      idx   = arange(-width, width + o, dtype=float64)[None, None] / o
+      t     = arange(0, -n, -1)[:, None, None] / n + idx        the int64 arange divided by an int is float32; the sum with idx is float64
+      t    *= base; t.clamp_(-lowpass_filter_width, lowpass_filter_width)
+      window = cos(t * pi / lowpass_filter_width / 2) ** 2
+      t    *= pi
+      k     = where(t == 0, 1.0, sin(t) / t) * window * (base / o)
+      table = k.to(float32)
+
+    The float32 phase term is deliberate: it is what the torch expression does; against a float64 phase it moves table entries by up to
+    1.9e-6 (44 100 Hz), 7.4e-6 (22 050 Hz), 1.4e-5 (11 025 Hz).  -> (table float32 [n, 1, 2 * width + o], width)."""
+    import math
+    o, n = _resample_ratio(orig_freq, new_freq)
+    lpw = int(lowpass_filter_width)
+    if lpw < 1 or not 0.0 < float(rolloff) <= 1.0:
+        raise ValueError(f"resample: lowpass_filter_width {lowpass_filter_width} / rolloff {rolloff}")
+    base = min(o, n) * float(rolloff)
+    width = math.ceil(lpw * o / base)
+    idx = torch.arange(-width, width + o, dtype=torch.float64)[None, None] / o
+    t = _resample_phase(n) + idx
+    t *= base
+    t.clamp_(-lpw, lpw)
+    window = torch.cos(t * math.pi / lpw / 2) ** 2
+    t *= math.pi
+    scale = base / o
+    k = torch.where(t == 0, torch.tensor(1.0, dtype=t.dtype), t.sin() / t)
+    k = k * window * scale
+    return k.to(torch.float32), width
+
+
+def resample_compact_table(table):
+    """The table as the kernel reads it.  In fp32 every phase's non-zero taps form one contiguous run (ValueError otherwise): per phase the
+    index `first` of the run's first tap and the run's weights, padded with the zeros that follow to K = the largest run of the table.
+    `first` is moved down to L - K where the run ends at the row's end, so that first + K <= L for every phase.  table float32 [n, 1, L] (or
+    [n, L]) -> (first int32 [n], weights float32 [n, K]), numpy."""
+    t = np.asarray(table, dtype=np.float32)
+    t = t.reshape(t.shape[0], t.shape[-1])
+    n, L = t.shape
+    nz = t != 0
+    if not nz.any(axis=1).all():
+        raise ValueError("resample: a phase of the table has no non-zero tap")
+    lo = nz.argmax(axis=1)
+    hi = L - nz[:, ::-1].argmax(axis=1)                                  # one past the last non-zero tap
+    if int((hi - lo).sum()) != int(nz.sum()):
+        raise ValueError("resample: the non-zero taps of a phase are not one contiguous run")
+    K = int((hi - lo).max())
+    first = np.minimum(lo, L - K).astype(np.int32)
+    weights = t[np.arange(n)[:, None], first[:, None] + np.arange(K)[None, :]]
+    return first, np.ascontiguousarray(weights)
+
+
+def resample_expand_table(first, weights, L):
+    """the dense [n, L] float32 table of a compact one (resample_compact_table's inverse)"""
+    first, weights = np.asarray(first), np.asarray(weights, dtype=np.float32)
+    n, K = weights.shape
+    t = np.zeros((n, int(L)), dtype=np.float32)
+    t[np.arange(n)[:, None], first[:, None] + np.arange(K)[None, :]] = weights
+    return t
+
+
+def resample_out_length(length, orig_freq, new_freq):
+    """ceil(n * length / o) in exact integers: the samples torchaudio's resample returns for `length` input samples"""
+    o, n = _resample_ratio(orig_freq, new_freq)
+    return -((-n * int(length)) // o)
+
+
+def resample_channels(x, table, width, o, n, m):
+    """outputs 0 .. m - 1 of every channel of one clip, before the channel mean: x float64 [C, len], table float64 [n, 2 width + o] ->
+    [C, m] with out[c, q n + p] = sum_m table[p, m] x[c, q o + m - width], samples outside the clip zero.  (Called with |table| and |x| it
+    gives the sum of the products' magnitudes: what the tests' error bounds are made of.)"""
+    C, ln = x.shape
+    L = table.shape[1]
+    nq = -(-int(m) // n) if m else 0
+    padded = np.zeros((C, width + nq * o + L), dtype=np.float64)
+    padded[:, width:width + ln] = x
+    acc = np.zeros((C, nq, n), dtype=np.float64)
+    for q in range(nq):
+        acc[:, q, :] = padded[:, q * o:q * o + L] @ table.T
+    return acc.reshape(C, nq * n)[:, :m]
+
+
+def resample_reference(wave, rates, lengths=None, new_freq=16000):
+    """The specification of ``ops.resample_wave`` in float64: what the reference's loader does to decoded audio ahead of the fbank
+    (dataloader_ft.py:272-277, 298-306) - torchaudio.functional.resample(waveform, sr, 16000) when sr != 16000, then waveform.mean(dim=0).
+
+    wave [B, C, stride] or [B, stride] (one channel); rates: an int or B ints, the clips' own sample rates; lengths [B] samples per clip
+    (None: stride).  Per clip of `len` samples at a rate with o = rate / gcd, n = new_freq / gcd and table [n, L], L = 2 width + o
+    (``resample_table_reference``; its fp32 values taken as doubles), per channel and output j = q n + p, 0 <= p < n:
+        out[j] = sum_m table[p, m] * x[q o + m - width]          for j < ceil(n len / o); samples outside 0 .. len - 1 count as zero
+    then the mean over the channels.  A clip whose rate equals new_freq is not filtered: only its channel mean is taken (the reference's
+    `if sr != 16000`).  Two quirks of the reference are NOT rebuilt (INTEGRATION.md 2(a'')): it hands the file's sr to the fbank after
+    resampling, and it resamples the mixup partner by the first file's sr.
+    -> (out float64 [B, out_stride], out_lengths int64 [B]); the tail of every row is zero; out_stride is the largest ceil(n stride / o) over
+    the call's rates."""
+    wave = np.asarray(wave)
+    if wave.ndim == 2:
+        wave = wave[:, None, :]
+    if wave.ndim != 3:
+        raise ValueError(f"resample: need [B, C, stride] or [B, stride], got {wave.shape}")
+    B, C, stride = wave.shape
+    rates = [int(rates)] * B if np.isscalar(rates) else [int(r) for r in rates]
+    if len(rates) != B:
+        raise ValueError(f"resample: {len(rates)} rates for {B} clips")
+    lengths = np.full(B, stride, dtype=np.int64) if lengths is None else np.asarray(lengths, dtype=np.int64).reshape(B)
+    if (lengths < 0).any() or (lengths > stride).any():
+        raise ValueError(f"resample: lengths must lie in 0 .. {stride}, got {lengths.tolist()}")
+    out_stride = max(resample_out_length(stride, r, new_freq) for r in rates)
+    out = np.zeros((B, out_stride), dtype=np.float64)
+    out_lengths = np.zeros(B, dtype=np.int64)
+    tables = {}
+    for b in range(B):
+        ln = int(lengths[b])
+        x = wave[b, :, :ln].astype(np.float64)
+        if rates[b] == int(new_freq):
+            out[b, :ln] = x.mean(axis=0)
+            out_lengths[b] = ln
+            continue
+        if rates[b] not in tables:
+            tab, width = resample_table_reference(rates[b], new_freq)
+            tables[rates[b]] = (tab[:, 0, :].numpy().astype(np.float64), width)
+        tab, width = tables[rates[b]]
+        o, n = _resample_ratio(rates[b], new_freq)
+        m = resample_out_length(ln, rates[b], new_freq)
+        out[b, :m] = resample_channels(x, tab, width, o, n, m).mean(axis=0)
+        out_lengths[b] = m
+    return out, out_lengths

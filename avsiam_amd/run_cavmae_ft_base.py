@@ -107,6 +107,11 @@ def build_parser():
     p.add_argument('--frame-size', dest="frame_size", type=int, nargs=2, default=None, metavar=("H", "W"),
                    help="with --wave-input: uint8 frames at the decoded size H x W, resized (antialiased bicubic), normalised and mixed on the device "
                         "(dataloader_ft.py:136-139, 434-459)")
+    p.add_argument('--sample-rate', dest="sample_rate", type=int, nargs='+', default=None, metavar="R",
+                   help="with --wave-input: the audio stays at the files' own rates (cycled over the clips of a batch) and is resampled to 16 kHz on the "
+                        "device (dataloader_ft.py:272-277)")
+    p.add_argument('--audio-channels', dest="audio_channels", type=int, default=None, metavar="C",
+                   help="with --wave-input --sample-rate: channels of the decoded audio, averaged on the device (dataloader_ft.py:298-306)")
     p.add_argument('--eval-frames', dest="eval_frames", action="store_true",
                    help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
     return p
@@ -190,6 +195,16 @@ def main(argv=None):
             raise SystemExit("--frame-size names the size of the decoded uint8 frames of --wave-input: pass it with --wave-input")
         if not all(1 <= x <= 2240 for x in args.frame_size):
             raise SystemExit(f"--frame-size {args.frame_size[0]} {args.frame_size[1]}: H and W lie in 1 .. 2240 (at most 10 x the model's 224)")
+    if args.sample_rate is not None or args.audio_channels is not None:
+        if not args.wave_input:
+            raise SystemExit("--sample-rate / --audio-channels name the decoded audio of --wave-input: pass them with --wave-input")
+        if args.sample_rate is None:
+            raise SystemExit("--audio-channels names the channels of the audio that --sample-rate resamples: pass --sample-rate with it (16000: only the "
+                             "channel mean is taken)")
+        if not all(1 <= r <= 768000 for r in args.sample_rate) or len(set(args.sample_rate)) > 8:
+            raise SystemExit(f"--sample-rate {' '.join(map(str, args.sample_rate))}: at most 8 distinct rates in 1 .. 768000 Hz")
+        if args.audio_channels is not None and not 1 <= args.audio_channels <= 8:
+            raise SystemExit(f"--audio-channels {args.audio_channels}: 1 .. 8")
     for w in inert_flag_warnings(args):
         print(w, flush=True)
     import random
@@ -231,10 +246,11 @@ def _run(args):
     if args.wave_input:
         from .traintest_ft_base import SyntheticWaveFtLoader
         norm = (args.dataset_mean, args.dataset_std)
+        source = {} if args.sample_rate is None else dict(sample_rate=args.sample_rate, channels=args.audio_channels or 1)
         train_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
-                                             mixup=args.mixup, norm=norm, train=True, frame_size=args.frame_size)
+                                             mixup=args.mixup, norm=norm, train=True, frame_size=args.frame_size, **source)
         val_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank,
-                                           label_smooth=args.label_smooth, frames=val_frames, norm=norm, train=False, frame_size=args.frame_size)
+                                           label_smooth=args.label_smooth, frames=val_frames, norm=norm, train=False, frame_size=args.frame_size, **source)
     else:
         train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
                                          raw=args.raw_input)

@@ -258,15 +258,31 @@ class SyntheticWaveFtLoader:
     frame_size=(H, W): the uint8 frames stay at the decoded size [B, frames, 3, H, W]; every batch draws a size per clip (and per partner) from
     FRAME_CROPS of (H, W) - the full frame or a narrower crop, so one padded buffer holds clips of several sizes - and ``v`` comes from
     ``ops.resize_frames`` (:136-139, 434-459: / 255, antialiased bicubic Resize to the model's size, Normalize, the mix with ``weight``); the
-    sizes are in ``last_draw`` as ``sizes`` / ``partner_sizes``.  None: frames at the model's size, as above."""
+    sizes are in ``last_draw`` as ``sizes`` / ``partner_sizes``.  None: frames at the model's size, as above.
+    sample_rate=R or [R, ...] (cycled over the clips of a batch), channels=C: the audio stays as decoded, float32 [B, C, samples * max R / 16 000]
+    at each clip's own rate, the drawn lengths scaled to it (``src_lengths`` / ``partner_src_lengths`` in ``last_draw``); every batch runs
+    ``ops.resample_wave`` (:272-277, 298-306: windowed-sinc resample to 16 kHz, channel mean) on the clips and on the partners, each by its own
+    rate, and hands the 16 kHz audio and its device-side lengths to the fbank call above.  None: the 16 kHz mono waveforms of before."""
 
     FRAME_CROPS = ((1.0, 1.0), (1.0, 0.75))                  # (h, w) fractions of frame_size a clip's size is drawn from
 
     def __init__(self, cfg, batch_size, steps, n_class, device, seed=87, label_smooth=0.1, frames=1, mixup=0.0, norm=(-5.081, 4.4849), train=True,
-                 samples=160000, frame_size=None):
+                 samples=160000, frame_size=None, sample_rate=None, channels=1):
         g = torch.Generator().manual_seed(seed)
         B = batch_size
         self.wave = (torch.randn(B, samples, generator=g) * 0.1).to(device)
+        self.rates = None
+        if sample_rate is None:
+            if int(channels) != 1:
+                raise ValueError("SyntheticWaveFtLoader: channels names the decoded audio of sample_rate=: pass a sample rate with it")
+        else:
+            sr = [sample_rate] if not hasattr(sample_rate, "__len__") else list(sample_rate)
+            if not sr or any(isinstance(r, bool) or int(r) != r or int(r) < 1 for r in sr) or not 1 <= int(channels) <= 8:
+                raise ValueError(f"SyntheticWaveFtLoader: sample_rate {sample_rate!r} (positive integers), channels {channels!r} (1 .. 8)")
+            self.rates = [int(sr[b % len(sr)]) for b in range(B)]
+            src = max(-((-samples * r) // 16000) for r in self.rates)
+            gs = torch.Generator().manual_seed(seed + 7919)      # its own stream: the frames and labels below are those of sample_rate=None
+            self.wave = (torch.randn(B, int(channels), src, generator=gs) * 0.1).to(device)
         self.frame_size = None if frame_size is None else (int(frame_size[0]), int(frame_size[1]))
         self.img_size = cfg.img_size
         fh, fw = self.frame_size or (cfg.img_size, cfg.img_size)
@@ -277,6 +293,7 @@ class SyntheticWaveFtLoader:
         self.mixup = float(mixup) if train else 0.0
         if self.mixup > 0:
             self.wave2, self.v2, self.hot2 = (torch.roll(t, 1, 0).contiguous() for t in (self.wave, self.v, self.hot))
+            self.rates2 = None if self.rates is None else self.rates[-1:] + self.rates[:-1]
         self.rng = np.random.default_rng(seed)
         self.steps, self.samples, self.norm, self.label_smooth, self.T = steps, samples, norm, label_smooth, cfg.audio_len
         self.last_draw = None
@@ -293,6 +310,10 @@ class SyntheticWaveFtLoader:
             d["partner_lengths"] = self.rng.integers(int(0.9 * self.samples), self.samples + 1, B).astype(np.int32)
             d["lam"] = np.where(mixed, self.rng.beta(10, 10, B), -1.0).astype(np.float32)
             d["weight"] = np.where(mixed, self.rng.random(B), 1.0).astype(np.float32)
+        if self.rates is not None:                           # (no draw of its own: the 16 kHz lengths at each clip's rate)
+            d["src_lengths"] = (d["lengths"].astype(np.int64) * np.asarray(self.rates) // 16000).astype(np.int32)
+            if self.mixup > 0:
+                d["partner_src_lengths"] = (d["partner_lengths"].astype(np.int64) * np.asarray(self.rates2) // 16000).astype(np.int32)
         if self.frame_size is not None:                      # (drawn last: the draws above are those of frame_size=None)
             crops = np.array([[max(1, round(self.frame_size[0] * fh)), max(1, round(self.frame_size[1] * fw))] for fh, fw in self.FRAME_CROPS], dtype=np.int32)
             d["sizes"] = crops[self.rng.integers(0, len(crops), B)]
@@ -304,14 +325,19 @@ class SyntheticWaveFtLoader:
         from . import ops, preprocess
         for _ in range(self.steps):
             d = self.last_draw = self.draw()
+            wave, lengths = self.wave, d["lengths"]
+            wave2, lengths2 = (self.wave2, d["partner_lengths"]) if self.mixup > 0 else (None, None)
+            if self.rates is not None:
+                wave, lengths = ops.resample_wave(self.wave, self.rates, d["src_lengths"])
+                if self.mixup > 0:
+                    wave2, lengths2 = ops.resample_wave(self.wave2, self.rates2, d["partner_src_lengths"])
             if self.mixup > 0:
-                a = ops.kaldi_fbank(self.wave, d["lengths"], partner=self.wave2, partner_lengths=d["partner_lengths"], lam=d["lam"],
-                                    target_length=self.T, norm=self.norm)
+                a = ops.kaldi_fbank(wave, lengths, partner=wave2, partner_lengths=lengths2, lam=d["lam"], target_length=self.T, norm=self.norm)
                 v = (ops.mix_frames(self.v, self.v2, d["weight"]) if self.frame_size is None else
                      ops.resize_frames(self.v, d["sizes"], partner=self.v2, partner_sizes=d["partner_sizes"], weight=d["weight"], size=self.img_size))
                 y = preprocess.mixup_labels(self.hot, self.hot2, torch.from_numpy(d["lam"]).to(self.hot.device), self.label_smooth)
             else:
-                a = ops.kaldi_fbank(self.wave, d["lengths"], target_length=self.T, norm=self.norm)
+                a = ops.kaldi_fbank(wave, lengths, target_length=self.T, norm=self.norm)
                 v = preprocess.normalize_frames(self.v) if self.frame_size is None else ops.resize_frames(self.v, d["sizes"], size=self.img_size)
                 y = preprocess.mixup_labels(self.hot, None, -1.0, self.label_smooth)
             yield a, v, y

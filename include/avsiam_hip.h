@@ -281,6 +281,24 @@ int avs_kaldi_fbank(const float* wave, long long stride, const int* len, const f
                     int use_norm, float mean, float std, avs_stream_t stream);
 int avs_fbank_tables(float* tab, int words);
 
+/* ---- source-rate audio (dataloader_ft.py:272-277, 298-306): torchaudio.functional.resample(waveform, sr, 16000) - windowed sinc, sinc_interp_hann,
+ * lowpass_filter_width 6, rolloff 0.99 - and waveform.mean(dim=0), in one launch.  The specification is avsiam_amd.preprocess.resample_reference
+ * (float64).  wave fp32 [B, C, stride], 1 <= C <= 8; len[b] samples per clip (DEVICE, NULL: stride; cut to 0 .. stride); tab_idx[b] (DEVICE):
+ * the clip's table, or -1 = pass-through (the clip is at the output rate: only the channel mean is taken).
+ *   tables   HOST array of n_tables <= 8 DEVICE pointers, geo HOST int[4 n_tables] = (o, n, width, taps) per table: o = rate / gcd, n = new rate /
+ *            gcd, the dense filter bank is [n, L], L = 2 width + o (preprocess.resample_table_reference; it is built in Python, never here).  A table
+ *            is COMPACT: int32 first[n], then float w[n][pitch], pitch = taps | 1: phase p's dense row is zero outside first[p] .. first[p] + taps - 1
+ *            and first[p] + taps <= L.  n * (pitch + 1) <= 16384 words, and the input span of a 1024-output tile,
+ *            (1023 / n + 2) * o + 2 width + 3 words, <= 16384 (avs_resample_plan gives both; -2 otherwise).
+ *   out      per channel, output j = q n + p: sum_m w[p][m] x[q o + first[p] + m - width] in fp32, taps in order (samples outside 0 .. len - 1 are
+ *            zero); the channels are added in order and divided once by C (C = 1: no division).  out[b, j] for j < out_len[b] =
+ *            ceil(n len / o) (64-bit integers), zero from there to out_stride.  Pass-through: out_len = len, out = the channel mean (C = 1: the
+ *            input's bytes).  out_stride >= ceil(n stride / o) of every table (-2 otherwise); a pass-through clip is cut to out_stride.
+ * One writer per cell, no atomics: two calls give identical bytes.  No synchronisation. */
+int avs_resample_plan(int o, int n, int width, int taps, int* table_words, int* span_words);
+int avs_resample_wave(const float* wave, int B, int C, long long stride, const int* len, const int* tab_idx, int n_tables,
+                      const void* const* tables, const int* geo, float* out, long long out_stride, int* out_len, avs_stream_t stream);
+
 /* ---- decoded-size frames (dataloader_ft.py:136-139, 434-459): frames / 255, Resize([224, 224], BICUBIC, antialias=True), Normalize and the frame
  * mix, from uint8 frames at the video's own size.  The specification is avsiam_amd.preprocess.resize_frames_reference (float64): torch's
  * interpolate(mode='bicubic', align_corners=False, antialias=True), no clamping.  Per axis with input size I and output size O, in float64:
