@@ -9,20 +9,34 @@
 // map, so gathering first is identical math.  Output rows are GEMM A-operands (bf16).
 // audio: a [B, time, mel] fp32; token = f*tP + t (:444-445 transpose -> image [mel, time]);
 //        out[r, p*16+q] = a[b, t*16+q, f*16+p]
+// The four gathers are templates on the output element: bf16 rows (GEMM A-operands of the bf16 path) or fp32 rows (the exact-fp32 forward,
+// exact.hip: the value the transform produces, unrounded).  The arithmetic in front of the store is one piece of code for both.
+__device__ __forceinline__ void im2col_store(bf16_t* p, float v) { *p = f2bf(v); }
+__device__ __forceinline__ void im2col_store(float* p, float v) { *p = v; }
+__device__ __forceinline__ void im2col_store4(bf16_t* p, const float4& x) {
+    uint2 o;
+    o.x = pack_bf2(x.x, x.y);
+    o.y = pack_bf2(x.z, x.w);
+    *reinterpret_cast<uint2*>(p) = o;
+}
+__device__ __forceinline__ void im2col_store4(float* p, const float4& x) { *reinterpret_cast<float4*>(p) = x; }
+
+template <typename OT>
 __global__ void im2col_audio_kernel(const float* __restrict__ a, const int* __restrict__ row_b,
-                                    const int* __restrict__ row_tok, bf16_t* __restrict__ out, int rows, int tlen,
+                                    const int* __restrict__ row_tok, OT* __restrict__ out, int rows, int tlen,
                                     int mel, int tP, InXf xf) {
     const int r = blockIdx.x;
     const int q = threadIdx.x >> 4, p = threadIdx.x & 15;      // consecutive threads read consecutive mel bins
     const int b = row_b[r], tok = row_tok[r];
     const int f = tok / tP, t = tok - f * tP;
     const float v = xf_audio(a, xf, b, t * 16 + q, f * 16 + p, tlen, mel);
-    out[(size_t)r * 256 + p * 16 + q] = f2bf(v);
+    im2col_store(out + (size_t)r * 256 + p * 16 + q, v);
 }
 
 // video: v [NF, C, H, W] fp32; token = gy*G + gx; out[r, c*256 + p*16 + q] = v[img, c, gy*16+p, gx*16+q]
+template <typename OT>
 __global__ void im2col_video_kernel(const void* __restrict__ vin, const int* __restrict__ row_img,
-                                    const int* __restrict__ row_tok, bf16_t* __restrict__ out, int rows, int C, int H,
+                                    const int* __restrict__ row_tok, OT* __restrict__ out, int rows, int C, int H,
                                     int W, int G, InXf xf) {
     const int r = blockIdx.x;
     const int img = row_img[r], tok = row_tok[r];
@@ -40,28 +54,27 @@ __global__ void im2col_video_kernel(const void* __restrict__ vin, const int* __r
             x = make_float4(((float)(w & 0xff) * (1.0f / 255.0f) - m) * is, ((float)((w >> 8) & 0xff) * (1.0f / 255.0f) - m) * is,
                             ((float)((w >> 16) & 0xff) * (1.0f / 255.0f) - m) * is, ((float)(w >> 24) * (1.0f / 255.0f) - m) * is);
         }
-        uint2 o;
-        o.x = pack_bf2(x.x, x.y);
-        o.y = pack_bf2(x.z, x.w);
-        *reinterpret_cast<uint2*>(out + (size_t)r * K + e) = o;
+        im2col_store4(out + (size_t)r * K + e, x);
     }
 }
 
 // The same gathers for a patch STRIDE S < 16 on 16 x 16 patch storage (config.stride: the 14 x 14 grid of ViT-H/14): token (t, f) / (gy, gx)
 // starts at pixel t*S / gy*S, only the S x S corner of the 256 positions per channel is read, the rest of the row is zero (so the padded
 // positions of the patch-embedding kernel never contribute and never receive a gradient).  Element-wise loads: S need not be a multiple of 4.
+template <typename OT>
 __global__ void im2col_audio_s_kernel(const float* __restrict__ a, const int* __restrict__ row_b, const int* __restrict__ row_tok,
-                                      bf16_t* __restrict__ out, int rows, int tlen, int mel, int tP, int S, InXf xf) {
+                                      OT* __restrict__ out, int rows, int tlen, int mel, int tP, int S, InXf xf) {
     const int r = blockIdx.x;
     const int q = threadIdx.x >> 4, p = threadIdx.x & 15;
     const int b = row_b[r], tok = row_tok[r];
     const int f = tok / tP, t = tok - f * tP;
     const float v = (q < S && p < S) ? xf_audio(a, xf, b, t * S + q, f * S + p, tlen, mel) : 0.f;
-    out[(size_t)r * 256 + p * 16 + q] = f2bf(v);
+    im2col_store(out + (size_t)r * 256 + p * 16 + q, v);
 }
 
+template <typename OT>
 __global__ void im2col_video_s_kernel(const void* __restrict__ vin, const int* __restrict__ row_img, const int* __restrict__ row_tok,
-                                      bf16_t* __restrict__ out, int rows, int C, int H, int W, int G, int S, InXf xf) {
+                                      OT* __restrict__ out, int rows, int C, int H, int W, int G, int S, InXf xf) {
     const int r = blockIdx.x;
     const int img = row_img[r], tok = row_tok[r];
     const int gy = tok / G, gx = tok - gy * G;
@@ -70,7 +83,7 @@ __global__ void im2col_video_s_kernel(const void* __restrict__ vin, const int* _
         const int c = e >> 8, p = (e >> 4) & 15, q = e & 15;
         float v = 0.f;
         if (p < S && q < S) v = xf_video(vin, xf, (((size_t)img * C + c) * H + gy * S + p) * W + gx * S + q, c);
-        out[(size_t)r * K + e] = f2bf(v);
+        im2col_store(out + (size_t)r * K + e, v);
     }
 }
 
@@ -523,7 +536,7 @@ extern "C" int avs_im2col_audio_xf(const float* a, const int* row_b, const int* 
     AVS_CHECK_ARG(rows > 0 && a && row_b && row_tok && out, "im2col_audio: bad args");
     InXf x;
     if (int rc = avs_make_xf(xf, 1, &x, "im2col_audio")) return rc;
-    im2col_audio_kernel<<<rows, 256, 0, stream>>>(a, row_b, row_tok, out, rows, tlen, mel, t_patches, x);
+    im2col_audio_kernel<bf16_t><<<rows, 256, 0, stream>>>(a, row_b, row_tok, out, rows, tlen, mel, t_patches, x);
     AVS_LAUNCH_CHECK("im2col_audio");
     return 0;
 }
@@ -539,7 +552,7 @@ extern "C" int avs_im2col_video_xf(const void* v, const int* row_img, const int*
     InXf x;
     if (int rc = avs_make_xf(xf, 2, &x, "im2col_video")) return rc;
     AVS_CHECK_ARG(x.kind == 0 || C == 3, "im2col_video: uint8 frames need 3 channels");
-    im2col_video_kernel<<<rows, 192, 0, stream>>>(v, row_img, row_tok, out, rows, C, H, W, W / 16, x);
+    im2col_video_kernel<bf16_t><<<rows, 192, 0, stream>>>(v, row_img, row_tok, out, rows, C, H, W, W / 16, x);
     AVS_LAUNCH_CHECK("im2col_video");
     return 0;
 }
@@ -555,7 +568,7 @@ extern "C" int avs_im2col_audio_s(const float* a, const int* row_b, const int* r
     AVS_CHECK_ARG(rows > 0 && a && row_b && row_tok && out && stride > 0 && stride < 16, "im2col_audio_s: bad args (stride %d)", stride);
     InXf x;
     if (int rc = avs_make_xf(xf, 1, &x, "im2col_audio_s")) return rc;
-    im2col_audio_s_kernel<<<rows, 256, 0, stream>>>(a, row_b, row_tok, out, rows, tlen, mel, t_patches, stride, x);
+    im2col_audio_s_kernel<bf16_t><<<rows, 256, 0, stream>>>(a, row_b, row_tok, out, rows, tlen, mel, t_patches, stride, x);
     AVS_LAUNCH_CHECK("im2col_audio_s");
     return 0;
 }
@@ -568,8 +581,34 @@ extern "C" int avs_im2col_video_s(const void* v, const int* row_img, const int* 
     InXf x;
     if (int rc = avs_make_xf(xf, 2, &x, "im2col_video_s")) return rc;
     AVS_CHECK_ARG(x.kind == 0 || C == 3, "im2col_video_s: uint8 frames need 3 channels");
-    im2col_video_s_kernel<<<rows, 256, 0, stream>>>(v, row_img, row_tok, out, rows, C, H, W, W / stride, stride, x);
+    im2col_video_s_kernel<bf16_t><<<rows, 256, 0, stream>>>(v, row_img, row_tok, out, rows, C, H, W, W / stride, stride, x);
     AVS_LAUNCH_CHECK("im2col_video_s");
+    return 0;
+}
+
+// fp32 rows out (the exact-fp32 forward, exact.hip / engine_exact.py): the same kernels instantiated on float, any stride 1..16, the same
+// read-side transforms.  The augmentation form has no fp32 instantiation.
+extern "C" int avs_im2col_audio_f32(const float* a, const int* row_b, const int* row_tok, float* out, int rows, int tlen, int mel,
+                                   int t_patches, int stride, const avs_input_xf_t* xf, hipStream_t stream) {
+    AVS_CHECK_ARG(rows > 0 && a && row_b && row_tok && out && stride > 0 && stride <= 16, "im2col_audio_f32: bad args (stride %d)", stride);
+    InXf x;
+    if (int rc = avs_make_xf(xf, 1, &x, "im2col_audio_f32")) return rc;
+    if (stride == 16) im2col_audio_kernel<float><<<rows, 256, 0, stream>>>(a, row_b, row_tok, out, rows, tlen, mel, t_patches, x);
+    else im2col_audio_s_kernel<float><<<rows, 256, 0, stream>>>(a, row_b, row_tok, out, rows, tlen, mel, t_patches, stride, x);
+    AVS_LAUNCH_CHECK("im2col_audio_f32");
+    return 0;
+}
+
+extern "C" int avs_im2col_video_f32(const void* v, const int* row_img, const int* row_tok, float* out, int rows, int C, int H, int W,
+                                   int stride, const avs_input_xf_t* xf, hipStream_t stream) {
+    AVS_CHECK_ARG(rows > 0 && v && row_img && row_tok && out && stride > 0 && stride <= 16 && (W % stride) == 0 && (H % stride) == 0,
+                  "im2col_video_f32: bad args (stride %d)", stride);
+    InXf x;
+    if (int rc = avs_make_xf(xf, 2, &x, "im2col_video_f32")) return rc;
+    AVS_CHECK_ARG(x.kind == 0 || C == 3, "im2col_video_f32: uint8 frames need 3 channels");
+    if (stride == 16) im2col_video_kernel<float><<<rows, 192, 0, stream>>>(v, row_img, row_tok, out, rows, C, H, W, W / 16, x);
+    else im2col_video_s_kernel<float><<<rows, 256, 0, stream>>>(v, row_img, row_tok, out, rows, C, H, W, W / stride, stride, x);
+    AVS_LAUNCH_CHECK("im2col_video_f32");
     return 0;
 }
 

@@ -11,6 +11,10 @@ B x T frames - so the 12 shared blocks are 12 x {LN(row-selected affine), QKV GE
 fc2} over all rows at once instead of one pass per modality.  The 10-frame evaluation loop of mm_grad becomes ONE packed
 batch of B x 10 (audio | frame t) sequences: the audio rows are written 10 times by the final LayerNorm's row map.
 No activation is kept (engine.Stack(inference=True)).
+
+exact=True (FtForward / Encoder / Head): the same schedule in fp32 end to end - engine_exact.ExactStack and ExactPatchEmbedder on the fp32
+master weights, the heads' GEMM straight on the master [label_dim, width].  The final norms, the scatter into the fusion stage, the token
+means and the L2 normalisation are fp32 in both forms and shared.
 """
 import torch
 
@@ -24,11 +28,19 @@ EVAL_FRAMES = 10        # `for t_idx in range(10)` at cav_mae_base.py:940
 
 class Head:
     """nn.Sequential(LayerNorm(width), Linear(width, label_dim)) (cav_mae_base.py:809-815).  The GEMM kernel wants N in
-    multiples of 128, so the bf16 weight copy is zero-padded to that (refresh() re-derives it from the fp32 master)."""
+    multiples of 128, so the bf16 weight copy is zero-padded to that (refresh() re-derives it from the fp32 master).
+    exact: fp32 LayerNorm output, the fp32 GEMM on the master weight itself - no padding, no copy, nothing to refresh."""
 
-    def __init__(self, arena: ParamArena, name, width, label_dim, max_rows, dev):
+    def __init__(self, arena: ParamArena, name, width, label_dim, max_rows, dev, exact=False):
         self.arena, self.name, self.width, self.L = arena, name, width, label_dim
         self.norm = Norm(arena, f"{name}.0")
+        self.exact = exact
+        if exact:
+            rp = ops.pad_rows(max_rows, 256)
+            self.h = _z((rp, width), F32, dev)
+            self.stat = [_z((rp,), F32, dev) for _ in range(2)]
+            self.out = _z((rp, label_dim), F32, dev)
+            return
         self.npad = ops.pad_rows(label_dim, 128)
         self.w = _z((self.npad, width), BF16, dev)
         self.b = _z((self.npad,), F32, dev)
@@ -39,12 +51,17 @@ class Head:
         self.refresh()
 
     def refresh(self):
+        if self.exact:
+            return
         self.w[:self.L].copy_(self.arena.w(f"{self.name}.1.weight"))
         self.b[:self.L].copy_(self.arena.w(f"{self.name}.1.bias"))
 
     def forward(self, x, n):
         """x: fp32 [>= n, width] pooled features -> fp32 [n, label_dim] logits (a view of the head's output buffer)."""
         ops.layernorm_fwd(x, self.norm.g, self.norm.b, self.h, self.stat[0], self.stat[1], n, LN_EPS_BLOCK)
+        if self.exact:
+            ops.gemm_nt_f32(self.h, self.arena.w(f"{self.name}.1.weight"), self.out, n, bias=self.arena.w(f"{self.name}.1.bias"))
+            return self.out[:n]
         ops.gemm_nt(self.h, self.w, self.out, n, bias=self.b)
         return self.out[:n, :self.L]
 
@@ -53,22 +70,28 @@ class Encoder:
     """The shared ViT over a packed batch of full sequences: `na` audio sequences (La tokens, '_a' norms) followed by
     `nv` frame sequences (Lv tokens, '_v' norms), then the per-modality final norm (cav_mae_base.py:832-841,853-860)."""
 
-    def __init__(self, arena, cfg: AVSiamConfig, na, nv, blocks, final, dev, inference=True, pool=None, opts=None):
-        """inference=False (ft_train.py): the stack keeps its activations for a backward (pool / opts: engine.Stack)."""
+    def __init__(self, arena, cfg: AVSiamConfig, na, nv, blocks, final, dev, inference=True, pool=None, opts=None, exact=False):
+        """inference=False (ft_train.py): the stack keeps its activations for a backward (pool / opts: engine.Stack).
+        exact: fp32 operands throughout (engine_exact; forward only)."""
         D, La, Lv = cfg.embed_dim, cfg.audio_tokens, cfg.video_tokens
         self.cfg, self.na, self.nv = cfg, na, nv
         self.rows_a, self.rows_v = na * La, nv * Lv
         self.rows = self.rows_a + self.rows_v
         self.blocks, self.final = blocks, final
         row_mod = torch.cat([torch.zeros(self.rows_a, dtype=U8), torch.ones(self.rows_v, dtype=U8)]).to(dev)
-        self.stack = make_stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, blocks, row_mod, inference=inference,
-                           pool=pool, opts=opts)
+        embedder = PatchEmbedder
+        if exact:
+            from .engine_exact import ExactPatchEmbedder as embedder, ExactStack
+            self.stack = ExactStack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, blocks, row_mod, inference=inference, pool=pool)
+        else:
+            self.stack = make_stack(dev, self.rows, D, cfg.num_heads, D * cfg.mlp_ratio, [La] * na + [Lv] * nv, blocks, row_mod, inference=inference,
+                                    pool=pool, opts=opts)
         self.emb_a = self.emb_v = None
         if na:
-            self.emb_a = PatchEmbedder(arena, dev, self.rows_a, True, cfg)
+            self.emb_a = embedder(arena, dev, self.rows_a, True, cfg)
             self.emb_a.set_rows(torch.arange(na).repeat_interleave(La).to(I32), torch.arange(La).repeat(na).to(I32))
         if nv:
-            self.emb_v = PatchEmbedder(arena, dev, self.rows_v, False, cfg)
+            self.emb_v = embedder(arena, dev, self.rows_v, False, cfg)
             self.emb_v.set_rows(torch.arange(nv).repeat_interleave(Lv).to(I32), torch.arange(Lv).repeat(nv).to(I32))
         self.yf = _z((self.stack.rp, D), F32, dev)              # final-norm output, fp32 token matrix
         self.fstat = [_z((self.stack.rp,), F32, dev) for _ in range(2)]
@@ -102,16 +125,17 @@ class Encoder:
 class FtForward:
     """All inference modes for one (batch, frames) shape; encoders are built on first use of a mode."""
 
-    def __init__(self, arena: ParamArena, cfg: AVSiamConfig, label_dim, batch, frames, dev):
+    def __init__(self, arena: ParamArena, cfg: AVSiamConfig, label_dim, batch, frames, dev, exact=False):
         self.arena, self.cfg, self.B, self.T, self.dev, self.L = arena, cfg, batch, frames, dev, label_dim
+        self.exact = exact
         D = cfg.embed_dim
         self.blocks = [BlockParams(arena, f"vit_base.blocks.{i}", "_a", "_v") for i in range(cfg.depth)]
         self.final = [Norm(arena, "vit_base.norm_a"), Norm(arena, "vit_base.norm")]
         self.blk_mm = [BlockParams(arena, "mm_layer_1", "_a"), BlockParams(arena, "mm_layer_2", "_a")]
         nmax = batch * max(frames, 1)
-        self.head_v = Head(arena, "mlp_head", D, label_dim, nmax, dev)
-        self.head_a = Head(arena, "mlp_head_a", D, label_dim, batch, dev)
-        self.head_mm = Head(arena, "mlp_head_mm", 2 * D, label_dim, nmax, dev)
+        self.head_v = Head(arena, "mlp_head", D, label_dim, nmax, dev, exact=exact)
+        self.head_a = Head(arena, "mlp_head_a", D, label_dim, batch, dev, exact=exact)
+        self.head_mm = Head(arena, "mlp_head_mm", 2 * D, label_dim, nmax, dev, exact=exact)
         self._enc = {}
         self._joint = {}
 
@@ -123,7 +147,7 @@ class FtForward:
         if kind not in self._enc:
             na = self.B if "a" in kind else 0
             nv = self.B * self.T if "v" in kind else 0
-            self._enc[kind] = Encoder(self.arena, self.cfg, na, nv, self.blocks, self.final, self.dev)
+            self._enc[kind] = Encoder(self.arena, self.cfg, na, nv, self.blocks, self.final, self.dev, exact=self.exact)
         return self._enc[kind]
 
     # ---- modes ---------------------------------------------------------------------------------------------------
@@ -155,7 +179,7 @@ class FtForward:
         B, T = self.B, self.T
         Lv = self.cfg.video_tokens
         if "av1" not in self._enc:                                 # ONE single-frame encoder; another frame_index only re-points the patch gather
-            enc = Encoder(self.arena, self.cfg, B, B, self.blocks, self.final, self.dev)
+            enc = Encoder(self.arena, self.cfg, B, B, self.blocks, self.final, self.dev, exact=self.exact)
             enc.norm = _z((2 * B,), F32, self.dev)
             enc.frame_index = None
             self._enc["av1"] = enc
@@ -176,7 +200,11 @@ class FtForward:
             La, Lv, D = cfg.audio_tokens, cfg.video_tokens, cfg.embed_dim
             Lj = La + Lv
             nseq = B * nf
-            st = make_stack(dev, nseq * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * nseq, self.blk_mm, inference=True)
+            if self.exact:
+                from .engine_exact import ExactStack
+                st = ExactStack(dev, nseq * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * nseq, self.blk_mm, inference=True)
+            else:
+                st = make_stack(dev, nseq * Lj, D, cfg.num_heads, D * cfg.mlp_ratio, [Lj] * nseq, self.blk_mm, inference=True)
             b = torch.arange(B).view(B, 1)
             i = torch.arange(La).view(1, La)
             maps_a = [((b * nf + t) * Lj + i).reshape(-1).to(I32).to(dev) for t in range(nf)]

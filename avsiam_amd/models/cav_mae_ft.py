@@ -209,13 +209,13 @@ class CAVMAEFT_BASE(nn.Module):
     def mark_weights_changed(self):
         self._shadow_dirty = True
 
-    def _engine(self, batch, frames):
-        key = (batch, frames)
+    def _engine(self, batch, frames, exact=False):
+        key = (batch, frames, True) if exact else (batch, frames)  # exact-fp32 engines share the cache and its limit
         if key not in self._engines:
             from ..ft_engine import FtForward
             while len(self._engines) >= MAX_ENGINES:               # serving with many batch shapes: drop the oldest buffers
                 self._engines.pop(next(iter(self._engines)))
-            self._engines[key] = FtForward(self.arena, self.cfg, self.label_dim, batch, frames, self.arena.p.device)
+            self._engines[key] = FtForward(self.arena, self.cfg, self.label_dim, batch, frames, self.arena.p.device, **({"exact": True} if exact else {}))
         else:
             self._engines[key] = self._engines.pop(key)            # most recently used last
         return self._engines[key]
@@ -595,20 +595,31 @@ class CAVMAEFT_BASE(nn.Module):
         self._rates = tuple(float(x) for x in state["lr"].tolist())
         self._dps = None                                           # (rebuilt from _opt at the next data-parallel step)
 
-    def forward(self, a, v, mode, is_eval=False, *, input_xf=None, aug=None):
+    def forward(self, a, v, mode, is_eval=False, *, input_xf=None, aug=None, exact=False):
         """a: [B, 1024, 128] fbank; v: [B, T, 3, 224, 224] frames (either may be None when the mode ignores it).
         Returns what the reference returns for the mode; any other mode returns None as there (no else branch).
         input_xf (extension, every mode): (ops.InputXf.audio(mean, std), ops.InputXf.frames()) - `a` is then the UN-normalised fbank and
         `v` uint8 frames as the reference's dataset holds them before its own arithmetic, normalised inside the kernels that read them.
         aug (extension, the training forms only): an ops.FtAug plan - SpecAugment masks, noise and time roll inside the audio patch gather
         (dataloader_ft.py:527-548, which the reference applies to the training set alone).  With input_xf=None the masks fall on the
-        normalised `a` (masked cells take aug.fill).  Refused with is_eval=True, in an inference-only mode and on a model without gradients."""
+        normalised `a` (masked cells take aug.fill).  Refused with is_eval=True, in an inference-only mode and on a model without gradients.
+        exact (extension, every mode): the exact-fp32 forward (engine_exact / csrc/exact.hip) - fp32 operands on the f32-input MFMA, read from
+        the fp32 master weights, with a fixed accumulation order: the logits are what an fp32 evaluation of the reference gives up to
+        summation order, a clip's result does not depend on its batch, and two calls give the same bytes.  Always an inference output (no
+        autograd node, whatever requires_grad says); refuses `aug`.  Slower than the bf16 path by the ratio of the matrix rates."""
         if mode not in MODES:
             return None
+        if exact and aug is not None:
+            raise ValueError("exact=True is an inference form: it takes no training augmentation (aug)")
         if not self.arena.p.is_cuda:
             raise _lib.AvsiamHipError("CAVMAEFT_BASE.forward needs a GPU: the path runs only on libavsiam_hip.so "
                                       "(no CPU/eager fallback). Move the model with .cuda() first.")
         _lib.load()
+        if exact:
+            with torch.no_grad():
+                xf = self._input_xf(input_xf, mode)
+                a, v, B, T = self._prepare(a, v, mode, xf)
+                return self._run_inference(self._engine(B, T, exact=True), a, v, mode, is_eval, xf, T)      # (masters are read: no shadow sync)
         if torch.is_grad_enabled() and mode in TRAIN_MODES and not is_eval:        # every is_eval form stays inference-only
             trainable = self._trainable()
             if trainable:
@@ -630,6 +641,10 @@ class CAVMAEFT_BASE(nn.Module):
         eng = self._engine(B, T)
         if self._shadow_dirty or self.arena.with_grads:
             self._sync_shadows()
+        return self._run_inference(eng, a, v, mode, is_eval, xf, T)
+
+    def _run_inference(self, eng, a, v, mode, is_eval, xf, T):
+        """the mode's engine call and the reference's output shapes (`eng`: the bf16 or the exact-fp32 FtForward)"""
         xfa = () if xf is None else (xf,)                          # (no transform: the engine calls of before, argument for argument)
         if mode == "audioonly":
             out = eng.audioonly(a, *xfa).clone()
@@ -647,12 +662,12 @@ class CAVMAEFT_BASE(nn.Module):
         return tuple(r.clone() for r in res)
 
     @torch.no_grad()
-    def retrieval_features(self, a, v, frame_index=5, out_a=None, out_v=None):
+    def retrieval_features(self, a, v, frame_index=5, out_a=None, out_v=None, exact=False):
         """Clip-level retrieval features: what the retrieval experiment makes of ``forward(a, v, "retrieval")`` (src/retrieval.py:70-78: mean
         over the tokens, L2 normalisation) -> (audio [B, D], video [B, D]) fp32 unit vectors.  Only frame `frame_index` of every clip goes
         through the encoder (frames are independent sequences, cav_mae_base.py:901-920), so any T > frame_index is accepted and a ten-frame
         clip costs 512 + 196 encoder rows instead of 512 + 1960.  out_a / out_v: fp32 [B, D] contiguous device tensors to write into
-        (row slices of a dataset-level feature buffer); None: new tensors."""
+        (row slices of a dataset-level feature buffer); None: new tensors.  exact: the exact-fp32 forward (see forward())."""
         if not self.arena.p.is_cuda:
             raise _lib.AvsiamHipError("CAVMAEFT_BASE.retrieval_features needs a GPU: the path runs only on libavsiam_hip.so "
                                       "(no CPU/eager fallback). Move the model with .cuda() first.")
@@ -669,6 +684,9 @@ class CAVMAEFT_BASE(nn.Module):
             elif t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (B, D) or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous fp32 [{B}, {D}] tensor on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
             outs.append(t)
+        if exact:
+            self._engine(B, T, exact=True).retrieval_feats(a, v, outs[0], outs[1], frame_index)
+            return outs[0], outs[1]
         eng = self._engine(B, T)
         if self._shadow_dirty or self.arena.with_grads:
             self._sync_shadows()

@@ -757,6 +757,66 @@ def im2col_video(v, row_img, row_tok, out, rows, xf=None, stride=16):
     _call("avs_im2col_video_s", v, row_img, row_tok, out, rows, C, H, W, int(stride), _xf_arg(xf, 2), _stream())
 
 
+# ---------------------------------------------------------------------------------------------------
+# exact-fp32 forward (csrc/exact.hip; engine_exact.py)
+def gemm_nt_f32(A, B, out, M, bias=None, res=None, res_idx=None, alpha=1.0, act=0):
+    """out[M,N] = act(alpha * (A[M,K] @ B[N,K]^T + bias + res[res_idx])), every operand fp32 (B: the arena's master weight itself).
+    act 0 | 1 (exact GELU on erff).  A, B, res and out are row views: the last dimension contiguous, the row stride free (A, B: a multiple of 4).
+    Any M, N >= 1; K % 32 == 0.  A fixed accumulation order per element (k-ordered chains per 32-wide slab, slab sums in slab order): a row's
+    result depends on nothing but that row."""
+    for t, name in ((A, "A"), (B, "B"), (out, "out"), (res, "res")):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != F32 or t.dim() != 2 or t.stride(1) != 1:
+            raise _lib.AvsiamHipError(f"gemm_f32.{name}: need a 2-D fp32 GPU tensor with contiguous rows, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    _chk(bias, F32, "gemm_f32.bias"); _chk(res_idx, I32, "gemm_f32.res_idx")
+    N, K = B.shape
+    if K % 32:
+        raise _lib.AvsiamHipError(f"gemm_nt_f32: K={K} is not a multiple of 32")
+    if act not in (0, 1):
+        raise _lib.AvsiamHipError(f"gemm_nt_f32: act must be 0 or 1, got {act}")
+    assert M >= 1 and A.shape[1] == K and A.shape[0] >= M and out.shape[0] >= M and out.shape[1] == N, (A.shape, B.shape, out.shape, M)
+    if bias is not None:
+        assert bias.numel() == N
+    if res is not None:
+        assert res.shape[1] == N
+        if res_idx is None:
+            assert res.shape[0] >= M
+        else:
+            assert res_idx.numel() >= M
+    else:
+        assert res_idx is None
+    _launch("gemm_nt_f32_act%d" % act, (2.0 * M * N * K, 4.0 * (M * K + N * K + M * N * (2 if res is not None else 1))), "avs_gemm_nt_f32", A, A.stride(0), B, B.stride(0),
+            M, N, K, bias, res, res.stride(0) if res is not None else 0, res_idx, out, out.stride(0), float(alpha), int(act), _stream())
+
+
+def attn_fwd_f32(qkv, tiles, H, out):
+    """softmax(hd^-0.5 q k^T) v per sequence over packed fp32 qkv [rows, 3 D] with UNscaled q -> fp32 out [rows, D]; tiles: AttnTiles."""
+    _chk(qkv, F32, "attn_f32.qkv", 2); _chk(out, F32, "attn_f32.out", 2)
+    D = qkv.shape[1] // 3
+    if qkv.shape[1] != 3 * D or D % H or D // H not in (32, 64, 80):
+        raise _lib.AvsiamHipError(f"attn_fwd_f32: qkv {tuple(qkv.shape)} with {H} heads: head dim must be 32, 64 or 80")
+    assert out.shape[1] == D and qkv.shape[0] >= tiles.max_row and out.shape[0] >= tiles.max_row and tiles.ntiles > 0
+    _launch("attn_fwd_f32_hd%d" % (D // H), (4.0 * tiles.sum_sq * D, tiles.rows * 16.0 * D), "avs_attn_fwd_f32", qkv, qkv.stride(0), D, H, tiles.start, tiles.len, tiles.q0,
+            tiles.ntiles, tiles.tile_rows, out, out.stride(0), _stream())
+
+
+def im2col_audio_f32(a, row_b, row_tok, out, rows, t_patches, xf=None, stride=16):
+    """im2col_audio with fp32 rows out (no augmentation form)"""
+    _chk(a, F32, "im2col.a", 3); _chk(row_b, I32, "im2col.row_b"); _chk(row_tok, I32, "im2col.row_tok"); _chk(out, F32, "im2col.out", 2)
+    assert out.shape[1] == 256 and out.shape[0] >= rows and row_b.numel() >= rows and row_tok.numel() >= rows
+    assert a.shape[1] == t_patches * stride and a.shape[2] % stride == 0
+    _call("avs_im2col_audio_f32", a, row_b, row_tok, out, rows, a.shape[1], a.shape[2], t_patches, int(stride), _xf_arg(xf, 1, a.shape[0]), _stream())
+
+
+def im2col_video_f32(v, row_img, row_tok, out, rows, xf=None, stride=16):
+    """im2col_video with fp32 rows out"""
+    _chk(v, U8 if xf is not None else F32, "im2col.v", 4); _chk(row_img, I32, "im2col.row_img"); _chk(row_tok, I32, "im2col.row_tok"); _chk(out, F32, "im2col.out", 2)
+    NF, C, H, W = v.shape
+    assert out.shape[1] == C * 256 and out.shape[0] >= rows and row_img.numel() >= rows and row_tok.numel() >= rows and W % stride == 0 and H % stride == 0
+    _call("avs_im2col_video_f32", v, row_img, row_tok, out, rows, C, H, W, int(stride), _xf_arg(xf, 2), _stream())
+
+
 PLAN_FIELDS = 16      # int32 per sequence descriptor of avs_mask_plan (csrc/maskplan.hip PlanSeq; fields 12..15: the grouped decoder layout)
 PLAN_CLASSIC = [-1, 0, 0, 0]      # fields 12..15 of a sequence in the classic (position-ordered) decoder layout
 

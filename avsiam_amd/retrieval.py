@@ -80,8 +80,8 @@ def _dataset_size(loader):
     return None
 
 
-def extract_features(audio_model, val_loader, frame_index=5):
-    """One pass over the loader -> (audio [N, D], video [N, D]) fp32 unit vectors on the model's device.  When the loader tells its size
+def extract_features(audio_model, val_loader, frame_index=5, exact=False):
+    """exact: features from the exact-fp32 forward (retrieval_features(exact=True); models that have the mode).  One pass over the loader -> (audio [N, D], video [N, D]) fp32 unit vectors on the model's device.  When the loader tells its size
     (``len(loader.dataset)`` or ``loader.num_clips``) every batch is written straight into its rows of the two [N, D] buffers."""
     import torch
     model = audio_model.module if hasattr(audio_model, "module") else audio_model
@@ -94,15 +94,16 @@ def extract_features(audio_model, val_loader, frame_index=5):
     if n is not None:
         fa, fv = torch.empty((n, D), dtype=torch.float32, device=dev), torch.empty((n, D), dtype=torch.float32, device=dev)
     chunks, at = [], 0
+    ex = {"exact": True} if exact else {}                           # (without the flag: the call of before, argument for argument)
     for batch in val_loader:
         a_input, v_input = batch[0], batch[1]
         B = a_input.shape[0]
         if fa is not None and at + B <= n:
-            model.retrieval_features(a_input, v_input, frame_index, out_a=fa[at:at + B], out_v=fv[at:at + B])
+            model.retrieval_features(a_input, v_input, frame_index, out_a=fa[at:at + B], out_v=fv[at:at + B], **ex)
         else:                                                       # size unknown (or misreported): keep the batches, join at the end
             if fa is not None:
                 chunks, fa, fv = [(fa[:at], fv[:at])], None, None
-            chunks.append(model.retrieval_features(a_input, v_input, frame_index))
+            chunks.append(model.retrieval_features(a_input, v_input, frame_index, **ex))
         at += B
     if fa is None:
         if not chunks:
@@ -132,13 +133,13 @@ def rank_features(fa, fv, direction="both", return_topk=0):
     return results, topk
 
 
-def get_retrieval_result(audio_model, val_loader, direction='audio', frame_index=5, return_topk=0):
+def get_retrieval_result(audio_model, val_loader, direction='audio', frame_index=5, return_topk=0, exact=False):
     """(R1, R5, R10, MR) of one direction as the reference (src/retrieval.py:62-92); direction='both': {'audio': (...), 'video': (...)} from
     ONE extraction pass.  return_topk=K (1..16): also the top-K gallery indices / similarities of every query (device tensors [N, K]), as a
-    second return value of the same form."""
+    second return value of the same form.  exact: extract_features(exact=True)."""
     if direction not in DIRECTIONS + ("both",):
         raise ValueError(f"direction must be 'audio', 'video' or 'both', not {direction!r}")
-    fa, fv = extract_features(audio_model, val_loader, frame_index)
+    fa, fv = extract_features(audio_model, val_loader, frame_index, **({"exact": True} if exact else {}))
     results, topk = rank_features(fa, fv, direction, return_topk)
     res = results if direction == "both" else results[direction]
     if return_topk:
@@ -227,6 +228,7 @@ def build_parser():
     p.add_argument("--dataset", type=str, default="synthetic", help="name written into the first column")
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="evaluate on N paired synthetic clips")
     p.add_argument("--seed", type=int, default=87)
+    p.add_argument("--exact", action="store_true", help="features from the exact-fp32 forward (fine-tuned models; slower)")
     return p
 
 
@@ -244,7 +246,7 @@ def main(argv=None):
     cfg = AVSiamConfig()
     net = load_model(args.model, args.num_class, args.model_type) if args.model else CAVMAEFT_BASE(label_dim=args.num_class).cuda()
     loader = SyntheticPairs(cfg, args.synthetic, args.batch_size, frames=args.frames, seed=args.seed, num_class=args.num_class, device=net.arena.p.device)
-    got = get_retrieval_result(net, loader, args.direction, args.frame_use, args.topk)
+    got = get_retrieval_result(net, loader, args.direction, args.frame_use, args.topk, **({"exact": True} if args.exact else {}))
     res, topk = got if args.topk else (got, None)
     if args.direction != "both":
         res, topk = {args.direction: res}, {args.direction: topk}

@@ -114,6 +114,8 @@ def build_parser():
                    help="with --wave-input --sample-rate: channels of the decoded audio, averaged on the device (dataloader_ft.py:298-306)")
     p.add_argument('--eval-frames', dest="eval_frames", action="store_true",
                    help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
+    p.add_argument('--exact-eval', dest="exact_eval", action="store_true",
+                   help="validation and --eval-frames forwards on the exact-fp32 path (fp32 operands from the master weights; slower, training unchanged)")
     return p
 
 

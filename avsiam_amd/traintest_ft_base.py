@@ -149,7 +149,8 @@ def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     Differences, deliberate: args.ftmode_test None (the launchers do not pass it; the reference would then select no mode and fail) falls back to
     args.ftmode; a two-dimensional output (videoonly with one frame squeezes its frame axis, :865) gets that axis back before the mean, where
     the reference would average over the classes.  args.device_metrics (absent: False): the stats
-    come from calculate_stats_device, and no [N, C] tensor is copied to the host.
+    come from calculate_stats_device, and no [N, C] tensor is copied to the host.  args.exact_eval (absent: False): the forwards run on the
+    exact-fp32 path (forward(..., exact=True)); evaluate_frames goes through here and follows it.
     Data parallel (the model has an active comm): predictions and targets of all ranks are gathered rank-major and truncated to
     len(val_sampler.dataset) when a sampler is given (distributed_concat, :22-27); every rank computes the same statistics; the loss stays
     this rank's own mean, as in the reference."""
@@ -159,6 +160,8 @@ def validate(audio_model, val_loader, val_sampler, args, output_pred=False):
     outs, tgts, losses = [], [], []
     xf = input_xf_of(args)
     extra = {"input_xf": xf} if xf is not None else {}     # never an augmentation: the reference augments the training set only
+    if getattr(args, "exact_eval", False):
+        extra["exact"] = True
     with torch.no_grad():
         for a_input, v_input, labels in val_loader:
             out = audio_model(a_input.to(device), v_input.to(device), mode, is_eval=True, **extra)

@@ -617,6 +617,26 @@ int avs_adam_table_sized(float* p, const float* g, float* m, float* v, avs_bf16*
 int avs_adam_table_set_lr(avs_adam_ctl* ctl, float lr_base, float lr_head, float lr_mm, avs_stream_t stream);
 int avs_adam_table_geometry(int* grid, int* chunk_elems, int* max_segs);
 
+/* ---- Exact-fp32 forward (csrc/exact.hip; engine_exact.py): the inference forms of the fine-tuned model with fp32 operands on the f32-input
+ * MFMA.  No atomics, no split-K, no shape-dependent accumulation order, no fast-math intrinsics: an output row depends on nothing but its own
+ * inputs, and two calls give the same bytes.
+ *  avs_gemm_nt_f32   out[M,N] = act(alpha * (A[M,K] . B[N,K]^T + bias + res[res_idx])); every operand fp32 with a leading dimension in
+ *                    elements (lda, ldb multiples of 4, A and B 16-byte aligned); bias / res / res_idx may be NULL (res_idx needs res);
+ *                    act 0 none | 1 exact GELU 0.5 x (1 + erff(x / sqrt 2)); any M, N >= 1; K % 32 == 0 (else -2).  Element (m, n): per
+ *                    32-wide K-slab one k-ordered fmaf chain, the slab sums added to one running total in ascending slab order.
+ *  avs_attn_fwd_f32  varlen softmax attention over packed fp32 qkv [rows, 3 D] (q UNscaled: hd^-0.5 is applied to the fp32 scores), tile
+ *                    tables (start, len, q0) as avs_attn_fwd, tile_rows 64 | 128, head dim 32 | 64 | 80 (else -2), out fp32 [rows, D].
+ *                    One workgroup per (tile, head); online softmax over 64-key tiles in ascending order.
+ *  avs_im2col_*_f32  the patch gathers of avs_im2col_*_s with fp32 rows out (stride 1..16, the same tables and input transforms) */
+int avs_gemm_nt_f32(const float* A, long long lda, const float* B, long long ldb, int M, int N, int K, const float* bias, const float* res,
+                    long long ldr, const int* res_idx, float* out, long long ldo, float alpha, int act, avs_stream_t stream);
+int avs_attn_fwd_f32(const float* qkv, long long ldq, int D, int H, const int* t_start, const int* t_len, const int* t_q0, int ntiles,
+                     int tile_rows, float* out, long long ldo, avs_stream_t stream);
+int avs_im2col_audio_f32(const float* a, const int* row_b, const int* row_tok, float* out, int rows, int tlen, int mel, int t_patches,
+                         int stride, const avs_input_xf* xf, avs_stream_t stream);
+int avs_im2col_video_f32(const void* v, const int* row_img, const int* row_tok, float* out, int rows, int C, int H, int W, int stride,
+                         const avs_input_xf* xf, avs_stream_t stream);
+
 /* ---- Collectives of the data-parallel path: thin wrappers over RCCL on a stream of the communicator's own, with event hand-off
  * (SURVEY.md 8(b)).  Replace, on the data path, torch.distributed's all_gather / all_reduce in GatherLayer
  * (src/models/gather_layer.py:21-37) and DistributedDataParallel's bucketed gradient all-reduce
