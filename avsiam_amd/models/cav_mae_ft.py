@@ -165,7 +165,9 @@ class CAVMAEFT_BASE(nn.Module):
         self._versions = None
         self._opt = None                                           # HIP Adam state of train_step / adam_step
         self._world, self._rank, self._comm, self._dp = 1, 0, None, False
-        self._dps = None                                           # data-parallel step state (_dp_state)
+        self._dps = None                                           # data-parallel / guarded step state (_dp_state)
+        self._guard_max = None                                     # set_grad_guard: max_norm of the guarded step; None: no guard
+        self._guard = None                                         # ops.GradGuard: the guard's device block (made at the first guarded step)
         self._rates = None                                         # (base, head, mm) learning rates of the last Adam step
         self._aug_seed = None                                      # set_aug_seed; None: derived from torch's seed at the first draw
         self._aug_st = None                                        # ops.FtAugState: the augmentation draws' key and counter, on the device
@@ -195,6 +197,7 @@ class CAVMAEFT_BASE(nn.Module):
             self._train_engines.clear()
             self._opt = None
             self._dps = None
+            self._guard = None
             self._aug_st, self._aug_plans = None, {}
             self._shadow_dirty = True
         return self
@@ -349,7 +352,7 @@ class CAVMAEFT_BASE(nn.Module):
         return names
 
     def train_step(self, a, v, labels, lr, ftmode="mm_grad", branch=None, loss="BCE", head_lr=1.0, mm_lr=1.0, beta1=0.95, beta2=0.999,
-                   eps=1e-8, weight_decay=5e-7, *, input_xf=None, aug=None):
+                   eps=1e-8, weight_decay=5e-7, *, input_xf=None, aug=None, guard=None):
         """One fused fine-tuning step (traintest_ft_base.py:133-175 without the host): the forward of the loss's branch only, the HIP
         classification loss, the backward and the HIP Adam of the reference's three groups.  -> the loss (device tensor [1], no sync).
         branch (mm_grad only): "mm" (loss on out), "a" (out_a: the audio encoder alone), "v" (out_v: the frame encoder alone).
@@ -359,7 +362,12 @@ class CAVMAEFT_BASE(nn.Module):
         live on the device (optimizer_steps()).
         input_xf = (ops.InputXf.audio(mean, std), ops.InputXf.frames()): `a` is the un-normalised fbank and `v` uint8 frames, normalised
         inside the patch gathers.  aug (ops.FtAug, e.g. draw_aug()): the step's SpecAugment masks, noise and time roll, applied inside the
-        audio patch gather - to the raw fbank with input_xf, to a normalised `a` without; ignored by the branches that read no audio ("v")."""
+        audio patch gather - to the raw fbank with input_xf, to a normalised `a` without; ignored by the branches that read no audio ("v").
+        Guarded (set_grad_guard, or guard = a max_norm for this call alone): between the gradients and Adam the device computes the gradient
+        norm, the clip_grad_norm_ coefficient and whether any gradient is inf or NaN; Adam scales the gradients by the coefficient, or - on a
+        non-finite gradient - writes nothing at all and keeps its step counts.  Still no host sync: guard_stats() reads the outcome.  A
+        guarded step takes the segment-table route of the data-parallel step on one rank too: ``.grad`` is left None after it, and the
+        step counts live on the device (optimizer_steps())."""
         from .. import ops
         from ..ft_train import OUT, OUT_A, OUT_V
         if ftmode not in TRAIN_MODES:
@@ -398,8 +406,9 @@ class CAVMAEFT_BASE(nn.Module):
             eng.loss_buf = (torch.zeros(max(n, B * T), dtype=torch.float32, device=x.device), torch.zeros(1, dtype=torch.float32, device=x.device))
         rows, out = eng.loss_buf
         ops.cls_loss(x, y, n, self.label_dim, ops.CLS_BCE if loss == "BCE" else ops.CLS_CE, rows, out, dx=head.dlog)
-        if self._dp:
-            self._dp_step(eng, cls_mode if mode != "mm_grad" else "mm_grad", bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay)
+        gmax = self._guard_max if guard is None else self._check_max_norm(guard)
+        if self._dp or gmax is not None:
+            self._dp_step(eng, cls_mode if mode != "mm_grad" else "mm_grad", bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, gmax)
             return out.clone()
         names = self._backward(eng, eng.token, cls_mode if mode != "mm_grad" else "mm_grad", bit if mode == "mm_grad" else (OUT_A if cls_mode == "audioonly" else OUT_V))
         self.adam_step(lr, head_lr, mm_lr, names, beta1, beta2, eps, weight_decay)
@@ -416,6 +425,8 @@ class CAVMAEFT_BASE(nn.Module):
             names = [n for n in self._trainable() if self._params[n].grad is not None and a.info[n].live]
         if not names:
             return
+        if self._dps is not None and not self._dp:                 # guarded steps counted on the device: the counts come back first (a sync)
+            self._drop_dp_state()
         lo0, hi0 = a.range[1]
         if self._opt is None:
             self._opt = {"m": torch.zeros(hi0 - lo0, device=a.p.device), "v": torch.zeros(hi0 - lo0, device=a.p.device), "step": {}}
@@ -462,6 +473,44 @@ class CAVMAEFT_BASE(nn.Module):
         if self.arena.p.is_cuda and _lib.env_value("AVSIAM_CU_RESERVE") is None:
             overlap = os.environ.get("AVSIAM_DP_OVERLAP", "1") != "0"
             _lib.tuning_set("cu_reserve", 8 if (self._dp and overlap) else 0)
+
+    # ---- the guarded step ---------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_max_norm(max_norm):
+        max_norm = float(max_norm)
+        if not max_norm > 0:
+            raise ValueError(f"max_norm must be > 0 (float('inf'): skip non-finite steps without clipping), not {max_norm}")
+        return max_norm
+
+    def set_grad_guard(self, max_norm=float("inf")):
+        """Guard every train_step from now on: gradients clipped to the total norm `max_norm` (torch.nn.utils.clip_grad_norm_; the default
+        inf never clips) and a step whose gradients hold inf or NaN skipped as a whole - weights, moments, bf16 shadows and step counts
+        keep their bytes (what the reference's GradScaler.step does, traintest_ft_base.py:162-165).  All of it on the device, between the
+        gradient all-reduce and Adam; data parallel, the norm is that of the rank-averaged gradients and every rank takes the same decision.
+        set_grad_guard(None) removes the guard: the step counts move back to the host (a sync, unless a data-parallel comm is active) and
+        train_step issues the calls it issued before.  The counters of guard_stats() start at the first guarded step."""
+        if max_norm is None:
+            self._guard_max = None
+            if not self._dp:
+                self._drop_dp_state()
+            return
+        self._guard_max = self._check_max_norm(max_norm)
+
+    def guard_stats(self):
+        """The guard's device block after the last guarded step, as host numbers.  SYNCHRONISES (one small copy behind everything queued on
+        the stream): call it where the loop syncs anyway.  -> norm (the total norm of the gradients Adam was given, before clipping),
+        norm_base / norm_head / norm_mm (per parameter group), coef (what the gradients were multiplied by; 0 on a skipped step),
+        n_nonfinite (inf / NaN gradient elements of the last step), skipped (the last step), n_skipped, n_steps (since the first guarded
+        step).  None before the first guarded step."""
+        if self._guard is None:
+            return None
+        r = self._guard.read()
+        scale = 1.0 / self._world if self._dp else 1.0
+        out = {"norm": r["norm"], "coef": r["coef"], "n_nonfinite": r["n_nonfinite"], "skipped": bool(r["skip"]), "n_skipped": r["n_skipped"],
+               "n_steps": r["n_steps"]}
+        for i, grp in enumerate(GROUPS):
+            out["norm_" + grp] = math.sqrt(float(r["sumsq"][i])) * scale
+        return out
 
     def _drop_dp_state(self):
         """forget the device state of the data-parallel step, keeping its step counts: the host dictionary is not maintained while ctl.step
@@ -524,16 +573,19 @@ class CAVMAEFT_BASE(nn.Module):
             if self._opt["step"]:                                  # steps taken before set_distributed: the counts move to the device
                 ctl.step.copy_(torch.tensor([self._opt["step"].get(c, 0) for c in CLASSES] + [0] * (ops.ADAM_TABLE_NCLS - len(CLASSES)),
                                             dtype=torch.int32))
-            st = self._dps = {"ctl": ctl, "trainable": None, "reducer": FixedScheduleReducer(self._comm, a.g, self.dp_schedule(), tail=ctl.live),
-                              "dead": {}, "livevec": {}}
+            # (one rank, guarded: the same state without a reducer - liveness is then what this rank's branch reaches)
+            red = FixedScheduleReducer(self._comm, a.g, self.dp_schedule(), tail=ctl.live) if self._dp else None
+            st = self._dps = {"ctl": ctl, "trainable": None, "reducer": red, "dead": {}, "livevec": {}}
         trainable = tuple(self._trainable())
         if st["trainable"] != trainable:
             st["table"] = self._adam_table(trainable)
             st["trainable"], st["dead"] = trainable, {}
         return st
 
-    def _dp_step(self, eng, cls_mode, bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay):
-        """Backward with the fixed-schedule all-reduce, liveness as its last message, and the one-launch Adam.  No host synchronisation."""
+    def _dp_step(self, eng, cls_mode, bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, max_norm=None):
+        """Backward with the fixed-schedule all-reduce, liveness as its last message, and the one-launch Adam.  No host synchronisation.
+        max_norm (a guarded step): avs_grad_sumsq over the summed gradients, then the guarded Adam.  Without an active comm (one rank,
+        guarded) there is no reducer: the same table, liveness set from the classes this branch reaches."""
         from .. import ops
         from ..comm import _union
         a = self.arena
@@ -544,23 +596,33 @@ class CAVMAEFT_BASE(nn.Module):
         names = [n for n in st["trainable"] if grad_class(n) in reach and a.info[n].live]
         cls = frozenset(grad_class(n) for n in names)
         base = any(param_group(n) == "base" for n in names)
-        if cls not in st["dead"]:
+        if red is not None and cls not in st["dead"]:
             # what this rank's backward never writes: every tensor outside the classes it reaches, and the frozen ones
             st["dead"][cls] = self.dp_dead_ranges(cls)
         if cls not in st["livevec"]:
             st["livevec"][cls] = torch.tensor([1.0 if c in cls else 0.0 for c in CLASSES] + [0.0] * (ops.ADAM_TABLE_NCLS - len(CLASSES)),
                                               dtype=torch.float32).to(a.p.device)
         ops.timed("torch_zero_grads", lambda: a.zero_grad_range(1))          # the WHOLE range: other ranks' classes arrive in it
-        red.begin(st["dead"][cls])
+        if red is not None:
+            red.begin(st["dead"][cls])
         eng.backward(eng.token, bit if names else 0, base=base, reducer=red)
         ctl.live.copy_(st["livevec"][cls])
-        red.finish()
+        if red is not None:
+            red.finish()
         self._rates = (lr, lr * head_lr, lr * mm_lr)
+        scale = 1.0 / self._world if red is not None else 1.0
         if st["table"] is not None:
             ctl.set_lr(*self._rates)
             m, v = self._opt["m"], self._opt["v"]
-            ops.adam_table(a.p[lo0:hi0], a.g[lo0:hi0], m, v, a.pb[lo0:hi0], st["table"], ctl, beta1, beta2, eps, weight_decay,
-                           grad_scale=1.0 / self._world)
+            if max_norm is None:
+                ops.adam_table(a.p[lo0:hi0], a.g[lo0:hi0], m, v, a.pb[lo0:hi0], st["table"], ctl, beta1, beta2, eps, weight_decay,
+                               grad_scale=scale)
+            else:
+                if self._guard is None:
+                    self._guard = ops.GradGuard(a.p.device)
+                ops.grad_sumsq(a.g[lo0:hi0], st["table"], ctl, self._guard, grad_scale=scale, max_norm=max_norm)
+                ops.adam_table_guarded(a.p[lo0:hi0], a.g[lo0:hi0], m, v, a.pb[lo0:hi0], st["table"], ctl, self._guard, beta1, beta2, eps,
+                                       weight_decay, grad_scale=scale)
         a.refresh_shadows(None, cast=False)
         for e in list(self._engines.values()) + list(self._train_engines.values()):
             e.refresh_heads()

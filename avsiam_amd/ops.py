@@ -1223,6 +1223,102 @@ def adam_table(p, g, m, v, p_bf16, table: AdamTable, ctl: AdamCtl, beta1=0.95, b
           float(weight_decay), float(grad_scale), _stream())
 
 
+# ---- the guard of the fine-tuning step: gradient norm, clipping coefficient, non-finite skip (csrc/grad_guard.hip) -----------------------------
+class GradGuard:
+    """avs_grad_guard on the device, {double sumsq[3], sumsq_cls[16], total; float norm, coef; int n_nonfinite, skip, n_skipped, n_steps}:
+    ONE 184-byte buffer with typed views, zeroed here (n_skipped and n_steps count from its creation), and the workspace of grad_sumsq,
+    grown when a table needs more."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(23, dtype=torch.float64, device=device)
+        self.sumsq, self.sumsq_cls, self.total = self.buf[:3], self.buf[3:3 + ADAM_TABLE_NCLS], self.buf[19:20]
+        tail = self.buf[20:]
+        self.norm, self.coef = tail.view(F32)[0:1], tail.view(F32)[1:2]
+        self.n_nonfinite, self.skip, self.n_skipped, self.n_steps = (tail.view(I32)[i:i + 1] for i in range(2, 6))
+        self.ws = None
+
+    def workspace(self, table):
+        """-> (buffer, bytes grad_sumsq needs for `table`)"""
+        need = _lib.load().avs_grad_sumsq_ws_bytes(len(table.segs), table.chunks)
+        if need == 0:
+            raise _lib.AvsiamHipError(f"grad_sumsq: no workspace size for {len(table.segs)} segments / {table.chunks} chunks")
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.zeros(need, dtype=U8, device=self.buf.device)
+        return self.ws, need
+
+    def read(self):
+        """the block as a dict of host numbers (synchronises)"""
+        import numpy as np
+        raw = self.buf.cpu().numpy()
+        f, i = raw[20:].view(np.float32), raw[20:].view(np.int32)
+        return {"sumsq": raw[:3].copy(), "sumsq_cls": raw[3:19].copy(), "total": float(raw[19]), "norm": float(f[0]), "coef": float(f[1]),
+                "n_nonfinite": int(i[2]), "skip": int(i[3]), "n_skipped": int(i[4]), "n_steps": int(i[5])}
+
+
+def grad_sumsq(g, table: AdamTable, ctl: AdamCtl, guard: GradGuard, grad_scale=1.0, max_norm=float("inf")):
+    """guard <- the squared norm of `g` over every segment of `table` whose class is live in `ctl` (fp64, non-finite elements counted and
+    left out), by group and by class, and from it norm = sqrt(total) * grad_scale, skip and the clip_grad_norm_ coefficient of max_norm
+    (include/avsiam_hip.h, avs_grad_sumsq).  Two launches on the current stream, no host sync."""
+    _chk(g, F32, "grad_sumsq.g")
+    _chk(table.dev, U8, "grad_sumsq.segs"); _chk(ctl.buf, F32, "grad_sumsq.ctl"); _chk(guard.buf, torch.float64, "grad_sumsq.guard")
+    assert g.numel() >= table.limit and g.data_ptr() % 16 == 0
+    if not max_norm > 0:
+        raise _lib.AvsiamHipError(f"grad_sumsq: max_norm must be > 0 (inf: no clipping), got {max_norm}")
+    ws, need = guard.workspace(table)
+    _call("avs_grad_sumsq", g, table.dev, len(table.segs), ctl.buf, float(grad_scale), float(max_norm), guard.buf, ws, need, _stream())
+
+
+def adam_table_guarded(p, g, m, v, p_bf16, table: AdamTable, ctl: AdamCtl, guard: GradGuard, beta1=0.95, beta2=0.999, eps=1e-8,
+                       weight_decay=5e-7, grad_scale=1.0):
+    """adam_table with the block grad_sumsq wrote: guard.skip set - nothing is written and ctl.step stays; otherwise the update with the
+    gradient scale fl32(grad_scale * guard.coef), read on the device."""
+    for t in (p, g, m, v):
+        _chk(t, F32, "adam_table_guarded")
+    _chk(p_bf16, BF16, "adam_table_guarded.p_bf16")
+    _chk(table.dev, U8, "adam_table_guarded.segs"); _chk(ctl.buf, F32, "adam_table_guarded.ctl")
+    _chk(guard.buf, torch.float64, "adam_table_guarded.guard")
+    assert all(t.numel() >= table.limit for t in (p, g, m, v)) and (p_bf16 is None or p_bf16.numel() >= table.limit)
+    assert all(t.data_ptr() % 16 == 0 for t in (p, g, m, v)) and (p_bf16 is None or p_bf16.data_ptr() % 8 == 0)
+    _call("avs_adam_table_guarded", p, g, m, v, p_bf16, table.dev, len(table.segs), table.chunks, ctl.buf, float(beta1), float(beta2),
+          float(eps), float(weight_decay), float(grad_scale), guard.buf, _stream())
+
+
+def grad_guard_reference(g, segs, live, grad_scale=1.0, max_norm=float("inf")):
+    """The numpy restatement of avs_grad_sumsq, the yardstick of its tests.  g: float array; segs: [(lo, n, group, cls), ...] - a segment that
+    breaks avs_adam_table's rules owns nothing; live: per-class liveness (> 0: live).  Sums in float64 by math.fsum (exactly rounded), the
+    coefficient in fp32 as the kernel and torch.nn.utils.clip_grad_norm_ write it.  -> dict with the fields of GradGuard.read() but the
+    cumulative counters, and norm64 / coef64: norm and coef without the fp32 roundings."""
+    import math
+    import numpy as np
+    g = np.asarray(g)
+    f32 = np.float32
+    by_group = [[] for _ in range(ADAM_TABLE_NGROUP)]
+    by_cls = [[] for _ in range(ADAM_TABLE_NCLS)]
+    bad = 0
+    for lo, n, grp, cls in segs:
+        if n <= 0 or n % 4 or lo < 0 or lo % 4 or not 0 <= grp < ADAM_TABLE_NGROUP or not 0 <= cls < ADAM_TABLE_NCLS:
+            continue
+        if not (cls < len(live) and live[cls] > 0):
+            continue
+        x = g[lo:lo + n].astype(np.float64)
+        fin = np.abs(x) <= float(np.finfo(np.float32).max) if g.dtype == np.float32 else np.isfinite(x)
+        bad += int((~fin).sum())
+        sq = (x[fin] * x[fin]).tolist()
+        by_group[grp] += sq
+        by_cls[cls] += sq
+    sumsq = np.array([math.fsum(s) for s in by_group], dtype=np.float64)
+    sumsq_cls = np.array([math.fsum(s) for s in by_cls], dtype=np.float64)
+    total = (sumsq[0] + sumsq[1]) + sumsq[2]
+    norm = f32(math.sqrt(total) * float(f32(grad_scale)))
+    skip = int(bad > 0)
+    with np.errstate(over="ignore"):
+        coef = f32(0.0) if skip else min(f32(1.0), f32(max_norm) / (norm + f32(1e-6)))
+    norm64 = math.sqrt(total) * float(grad_scale)                 # the same two formulas before the block's fp32 roundings
+    coef64 = 0.0 if skip else min(1.0, float(max_norm) / (norm64 + 1e-6))
+    return {"sumsq": sumsq, "sumsq_cls": sumsq_cls, "total": float(total), "norm": float(norm), "coef": float(coef), "n_nonfinite": bad,
+            "skip": skip, "norm64": norm64, "coef64": coef64}
+
+
 # ---- retrieval evaluation -------------------------------------------------------------------------------------------------------------
 RETRIEVAL_MAX_TOPK = 16
 _retr_ws = {}            # (device, stream) -> cached workspace: calls on different streams never share one; grown when a call needs more, so no

@@ -34,6 +34,10 @@ LOCAL_RANK form the process group (utils.init_distributed_mode), the model gets 
 synthetic shard, rank 0 writes the artefacts.  --world_size N without that environment starts nothing and is refused.  --force-dp: issue
 the collectives at world size 1 too (what one GPU can run of this path).  No run with more than one rank on RCCL exists: what is verified
 is the arithmetic and the message schedule (gloo ranks sharing one GPU), not the scaling.
+--clip-grad-norm X / --skip-nonfinite: the guarded step (CAVMAEFT_BASE.set_grad_guard) - the gradient norm, torch's clip_grad_norm_
+coefficient and the reference's skip of a step with inf / NaN gradients (GradScaler.step, traintest_ft_base.py:162-165), all on the device
+between the gradient all-reduce and Adam; the print steps add the norm, the coefficient and the steps skipped, and a run that skips more
+than half of its steps between two prints ends with "training diverged...".
 --pretrain_path <dir>/best_audio_model.pth also restores <dir>/best_optim_state.pth (Adam moments, per-class steps) when it is there and
 is a fine-tuning state of this model; the pre-training loop's file of the same name (torch.optim.Adam's format) is left alone.
 """
@@ -116,6 +120,11 @@ def build_parser():
                    help="after training: per-frame and frame-ensemble metric of the validation clips -> exp_dir/mul_frame_res.csv (mm_grad test mode)")
     p.add_argument('--exact-eval', dest="exact_eval", action="store_true",
                    help="validation and --eval-frames forwards on the exact-fp32 path (fp32 operands from the master weights; slower, training unchanged)")
+    p.add_argument('--clip-grad-norm', dest="clip_grad_norm", type=float, default=None, metavar="X",
+                   help="clip the total gradient norm to X on the device (torch.nn.utils.clip_grad_norm_) and skip steps with inf / NaN gradients")
+    p.add_argument('--skip-nonfinite', dest="skip_nonfinite", action="store_true",
+                   help="skip steps whose gradients hold inf or NaN, without clipping (what the reference's GradScaler.step does, "
+                        "traintest_ft_base.py:162-165)")
     return p
 
 
@@ -190,6 +199,8 @@ def main(argv=None):
     if args.wave_input and args.raw_input:
         raise SystemExit("--wave-input and --raw-input both name the loader's output (waveforms + uint8 frames | un-normalised fbank + uint8 frames): "
                          "pass one of them")
+    if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
+        raise SystemExit(f"--clip-grad-norm {args.clip_grad_norm}: a total gradient norm > 0")
     if args.wave_input and not 0.0 <= args.mixup <= 1.0:
         raise SystemExit(f"--mixup {args.mixup}: a probability")
     if args.frame_size is not None:

@@ -55,6 +55,22 @@ def train_step(model, a, v, labels, lr, ftmode, branch=None, loss="BCE", head_lr
     return model.train_step(a, v, labels, lr, ftmode, branch=branch, loss=loss, head_lr=head_lr, mm_lr=head_lr if mm_lr is None else mm_lr, **extra)
 
 
+def guard_max_norm(args):
+    """-> the max_norm of the guarded step the launcher's flags ask for: --clip-grad-norm X gives X (and skips non-finite steps, as every
+    guarded step does), --skip-nonfinite alone inf (never clips), neither None (no guard: the plain step)"""
+    clip = getattr(args, "clip_grad_norm", None)
+    if clip is not None:
+        if not float(clip) > 0:
+            raise SystemExit(f"--clip-grad-norm {clip}: a total gradient norm > 0")
+        return float(clip)
+    return float("inf") if getattr(args, "skip_nonfinite", False) else None
+
+
+def guard_diverged(steps, skipped):
+    """more than half of the steps since the last print were skipped for non-finite gradients"""
+    return steps > 0 and 2 * skipped > steps
+
+
 def input_xf_of(args):
     """the raw-input transforms of a run (args.raw_input): (InputXf.audio(dataset_mean, dataset_std), InputXf.frames()), else None"""
     if not getattr(args, "raw_input", False):
@@ -362,7 +378,13 @@ class _LrHolder:
 def train(audio_model, train_loader, test_loader, test_sampler, args):
     """train of the reference (:29-290) with the fused step.  args: ftmode, loss, lr, head_lr, mm_lr, freeze_base, n_epochs, lr_adapt,
     lr_patience, lrscheduler_start / _step / _decay, metrics, exp_dir, save_model, n_print_steps; optional freqm, timem, noise (the
-    per-step augmentation of the training batches), raw_input with dataset_mean / dataset_std."""
+    per-step augmentation of the training batches), raw_input with dataset_mean / dataset_std; optional clip_grad_norm (a max_norm) and
+    skip_nonfinite: the guarded step (CAVMAEFT_BASE.set_grad_guard) - at print steps, where the loss is read anyway, the gradient norm, the
+    clipping coefficient and the steps skipped so far are printed too, and a run that skipped more than half of the steps since the last
+    print ends with the reference's "training diverged..." (:184-186; there a NaN loss average) and "diverged": True in the result."""
+    max_norm = guard_max_norm(args)
+    if max_norm is not None:
+        audio_model.set_grad_guard(max_norm)
     world = getattr(audio_model, "_world", 1)
     if getattr(args, "world_size", 1) > 1 and world != args.world_size:
         raise SystemExit(f"data-parallel fine-tuning: args.world_size is {args.world_size} but the model's collectives are set for {world} rank(s) "
@@ -384,6 +406,7 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
     best_mAP, best_acc, best_epoch = -np.inf, -np.inf, 0
     result = np.zeros([args.n_epochs, 4])
     global_step, stale = 0, 0
+    seen_steps, seen_skipped = 0, 0                        # the guard's counters at the last print step
     xf = input_xf_of(args)
     freqm, timem, noise = int(getattr(args, "freqm", 0) or 0), int(getattr(args, "timem", 0) or 0), bool(getattr(args, "noise", False))
     augment = (freqm > 0 or timem > 0 or noise) and args.ftmode != "videoonly"
@@ -404,6 +427,14 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
             global_step += 1
             if global_step % args.n_print_steps == 0:
                 say(f"Epoch: [{epoch}][{global_step}] train loss {float(losses[-1]):.5f}", flush=True)
+                gs = audio_model.guard_stats() if max_norm is not None else None      # (the loss was just read: the stream is drained)
+                if gs is not None:
+                    say(f"Epoch: [{epoch}][{global_step}] grad norm {gs['norm']:.5g} (base {gs['norm_base']:.5g} head {gs['norm_head']:.5g} "
+                        f"mm {gs['norm_mm']:.5g}) clip coef {gs['coef']:.5g} skipped {gs['n_skipped']} of {gs['n_steps']} steps", flush=True)
+                    if guard_diverged(gs["n_steps"] - seen_steps, gs["n_skipped"] - seen_skipped):
+                        say("training diverged...", flush=True)
+                        return {"best_epoch": best_epoch, "best_mAP": best_mAP, "best_acc": best_acc, "result": result, "diverged": True}
+                    seen_steps, seen_skipped = gs["n_steps"], gs["n_skipped"]
         train_loss = float(torch.stack(losses).mean()) if losses else float("nan")
         stats, valid_loss = validate(audio_model, test_loader, test_sampler, args)
         mAP = float(np.nanmean([s["AP"] for s in stats]))

@@ -617,6 +617,43 @@ int avs_adam_table_sized(float* p, const float* g, float* m, float* v, avs_bf16*
 int avs_adam_table_set_lr(avs_adam_ctl* ctl, float lr_base, float lr_head, float lr_mm, avs_stream_t stream);
 int avs_adam_table_geometry(int* grid, int* chunk_elems, int* max_segs);
 
+/* ---- the guard of the fine-tuning step (csrc/grad_guard.hip): gradient norm, clipping coefficient and non-finite skip on the device, between
+ * the gradients and Adam.  Semantics: torch.nn.utils.clip_grad_norm_(parameters, max_norm) - total_norm = ||g||_2 over every gradient,
+ * clip_coef = clamp(max_norm / (total_norm + 1e-6), max = 1) - and the reference's scaler.step(optimizer), src/traintest_ft_base.py:115,162-165
+ * (torch.cuda.amp.GradScaler: the optimizer is not called when a gradient holds inf or NaN).
+ *  avs_grad_sumsq   over the table and control block of avs_adam_table, under its rules: malformed segments own nothing, segments of classes
+ *                   with live[c] <= 0 and the gaps are not read.  Stage 1, one workgroup per chunk of chunk_elems elements (grid-strided, 16-byte
+ *                   loads): the finite elements squared and summed in fp64, the others (!(|x| <= FLT_MAX)) counted and left out; one record per
+ *                   chunk in ws, one writer.  Stage 2, one workgroup: the records added in an order fixed by the geometry, then *guard written:
+ *                     sumsq[group], sumsq_cls[cls]   sums of squares of the UNSCALED gradients per lr group and per class
+ *                     total        sumsq[0] + sumsq[1] + sumsq[2], in that order
+ *                     norm         (float)(sqrt(total) * (double)grad_scale): the norm of the gradients Adam applies
+ *                     n_nonfinite  elements left out; -1: the table has more chunks than ws holds (nothing was written past ws; skip is set)
+ *                     skip         n_nonfinite != 0
+ *                     coef         skip ? 0 : fminf(1.0f, max_norm / (norm + 1e-6f)), in fp32; max_norm = +inf gives exactly 1.0f
+ *                     n_skipped += skip, n_steps += 1   cumulative: zero the block once, before its first use
+ *                   No floating-point atomics: two calls give identical bytes.  ws: avs_grad_sumsq_ws_bytes(n_segs, n_chunks) bytes, n_chunks the
+ *                   table's chunk count (avs_adam_table_sized); 16-byte aligned, as g.  The stage-1 grid is min(records ws holds, the geometry's grid).
+ *                   NULL g / segs / ctl / guard / ws, n_segs out of range, max_norm not > 0, a non-finite grad_scale, ws_bytes below one record:
+ *                   -2 before any launch.  avs_grad_sumsq_ws_bytes: 0 for arguments out of range.
+ *  avs_adam_table_guarded   avs_adam_table_sized with the block avs_grad_sumsq wrote: every workgroup reads guard->skip and guard->coef once.
+ *                   skip: nothing is written - not p, m, v or p_bf16 - and the step-count kernel leaves ctl->step alone.  Otherwise the update
+ *                   with the gradient scale grad_scale * coef (one fp32 multiply): the bytes avs_adam_table_sized leaves when it is given that
+ *                   product as its grad_scale.  NULL guard: -2. */
+typedef struct avs_grad_guard {
+    double sumsq[3];
+    double sumsq_cls[16];
+    double total;
+    float norm, coef;
+    int n_nonfinite, skip, n_skipped, n_steps;
+} avs_grad_guard;
+int avs_grad_sumsq(const float* g, const avs_adam_seg* segs, int n_segs, const avs_adam_ctl* ctl, float grad_scale, float max_norm,
+                   avs_grad_guard* guard, void* ws, size_t ws_bytes, avs_stream_t stream);
+size_t avs_grad_sumsq_ws_bytes(int n_segs, long long n_chunks);
+int avs_adam_table_guarded(float* p, const float* g, float* m, float* v, avs_bf16* p_bf16, const avs_adam_seg* segs, int n_segs,
+                           long long n_chunks, avs_adam_ctl* ctl, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                           const avs_grad_guard* guard, avs_stream_t stream);
+
 /* ---- Exact-fp32 forward (csrc/exact.hip; engine_exact.py): the inference forms of the fine-tuned model with fp32 operands on the f32-input
  * MFMA.  No atomics, no split-K, no shape-dependent accumulation order, no fast-math intrinsics: an output row depends on nothing but its own
  * inputs, and two calls give the same bytes.

@@ -23,6 +23,13 @@ into a second tensor, then the plain step).  All three read a normalised fbank, 
     python tools/bench_ft_train.py --aug --plain-only --tree <checkout of another commit, built> [--label parent]
 the plain step alone with the package of another tree (the parent commit, which has no augmentation to time): run it alternately with the
 line above and compare "plain" with "plain".
+
+    python tools/bench_ft_train.py --guard [--out profiles/rNN/grad_guard_bench.json]
+the guarded step (set_grad_guard): avs_grad_sumsq alone on the table of a mm step, as a fraction of the float4-copy rate on its 4 B per
+element; the Adam phase guarded (grad_sumsq + adam_table_guarded) against unguarded (adam_table); the whole mm step guarded (max_norm 1.0,
+so the coefficient is in play) against plain.  Seven rounds, the ways interleaved inside a round; median and min - max of the rounds.
+    python tools/bench_ft_train.py --guard --plain-only --tree <checkout of another commit, built> [--label parent]
+the plain step alone with the package of another tree: run it alternately with `--guard --plain-only` of this one.
 """
 import argparse
 import json
@@ -165,6 +172,82 @@ def _aug(args):
     return res
 
 
+GUARD_ROUNDS = 7
+COPY_RATE = 6.29e12          # B/s, the float4-copy rate of the README's other HBM-bound kernels (read + write)
+
+
+def _med(xs):
+    ys = sorted(xs)
+    return {"median": round(ys[len(ys) // 2], 4), "min": round(ys[0], 4), "max": round(ys[-1], 4), "rounds": [round(x, 4) for x in xs]}
+
+
+def _guard(args):
+    from avsiam_amd.config import AVSiamConfig
+    from avsiam_amd.models import CAVMAEFT_BASE
+    from avsiam_amd.traintest_ft_base import SyntheticFtLoader, apply_freeze_base
+    import avsiam_amd
+    cfg, L = AVSiamConfig(), 527
+    res = {"metric": "ft_grad_guard", "label": args.label, "package": os.path.dirname(os.path.abspath(avsiam_amd.__file__)),
+           "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "rounds": GUARD_ROUNDS, "results": {}}
+    kw = dict(head_lr=100.0, mm_lr=100.0)
+    for B in [int(b) for b in args.batches.split(",")]:
+        plain = CAVMAEFT_BASE(L).cuda()
+        apply_freeze_base(plain, False)
+        ld = SyntheticFtLoader(cfg, B, 1, L, plain.arena.p.device)
+        ways = {"plain_ms": lambda i: plain.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch="mm", **kw)}
+        if not args.plain_only:
+            from avsiam_amd import ops
+            from avsiam_amd.models.cav_mae_ft import CLASSES
+            g = CAVMAEFT_BASE(L).cuda()
+            apply_freeze_base(g, False)
+            g.set_grad_guard(1.0)
+            g.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch="mm", **kw)          # builds the table; a mm step's gradients in the arena
+            a, st = g.arena, g._dps
+            lo0, hi0 = a.range[1]
+            table, ctl, guard = st["table"], st["ctl"], g._guard
+            mom = (g._opt["m"], g._opt["v"])
+            live = ctl.live.cpu().tolist()
+            n_live = int(sum(n for _, n, _, c in table.segs if live[c] > 0))
+
+            def refresh():
+                a.refresh_shadows(None, cast=False)
+                for e in list(g._engines.values()) + list(g._train_engines.values()):
+                    e.refresh_heads()
+
+            def adam_plain(i):
+                ctl.set_lr(1e-4, 1e-2, 1e-2)
+                ops.adam_table(a.p[lo0:hi0], a.g[lo0:hi0], *mom, a.pb[lo0:hi0], table, ctl)
+                refresh()
+
+            def adam_guarded(i):
+                ctl.set_lr(1e-4, 1e-2, 1e-2)
+                ops.grad_sumsq(a.g[lo0:hi0], table, ctl, guard, max_norm=1.0)
+                ops.adam_table_guarded(a.p[lo0:hi0], a.g[lo0:hi0], *mom, a.pb[lo0:hi0], table, ctl, guard)
+                refresh()
+
+            ways.update(guarded_ms=lambda i: g.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch="mm", **kw),
+                        grad_sumsq_ms=lambda i: ops.grad_sumsq(a.g[lo0:hi0], table, ctl, guard, max_norm=1.0),
+                        adam_phase_plain_ms=adam_plain, adam_phase_guarded_ms=adam_guarded)
+        t = {k: [] for k in ways}
+        for _ in range(GUARD_ROUNDS):
+            for k, fn in ways.items():
+                mult = 20 if k == "grad_sumsq_ms" else 1             # (two short launches: a window of 20 x steps calls, not of a millisecond)
+                t[k].append(_time(fn, args.steps * mult, args.warmup))
+        r = {k: _med(x) for k, x in t.items()}
+        if not args.plain_only:
+            us = r["grad_sumsq_ms"]["median"] * 1e3
+            r["grad_sumsq"] = {"elements_live": n_live, "table_segments": len(table.segs), "chunks": table.chunks, "median_us": round(us, 2),
+                               "floor_us_derived": round(4.0 * n_live / COPY_RATE * 1e6, 2),
+                               "fraction_of_copy_rate": round(4.0 * n_live / (us * 1e-6) / COPY_RATE, 4),
+                               "live_classes": [c for i, c in enumerate(CLASSES) if live[i] > 0]}
+            r["guard_stats"] = g.guard_stats()
+            del g
+        res["results"][f"batch_{B}"] = r
+        del plain
+        torch.cuda.empty_cache()
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -173,17 +256,18 @@ def main(argv=None):
     ap.add_argument("--adam-table", dest="adam_table", action="store_true")
     ap.add_argument("--dp-one-rank", dest="dp_one_rank", action="store_true")
     ap.add_argument("--aug", action="store_true", help="the mm / a steps plain, with the fused augmentation and with the two-pass one")
-    ap.add_argument("--plain-only", dest="plain_only", action="store_true", help="with --aug: time the plain step only")
-    ap.add_argument("--tree", type=str, default=None, help="with --aug --plain-only: import avsiam_amd from this checkout")
+    ap.add_argument("--guard", action="store_true", help="grad_sumsq alone, the Adam phase and the mm step guarded against plain")
+    ap.add_argument("--plain-only", dest="plain_only", action="store_true", help="with --aug / --guard: time the plain step only")
+    ap.add_argument("--tree", type=str, default=None, help="with --aug / --guard and --plain-only: import avsiam_amd from this checkout")
     ap.add_argument("--label", type=str, default=None, help="copied into the result")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON result to this file")
     args = ap.parse_args(argv)
     if args.tree:
-        if not (args.aug and args.plain_only):
-            ap.error("--tree goes with --aug --plain-only")
+        if not ((args.aug or args.guard) and args.plain_only):
+            ap.error("--tree goes with --aug --plain-only or --guard --plain-only")
         sys.path.insert(0, os.path.abspath(args.tree))
-    if args.adam_table or args.dp_one_rank or args.aug:
-        res = (_adam_table if args.adam_table else _dp_one_rank if args.dp_one_rank else _aug)(args)
+    if args.adam_table or args.dp_one_rank or args.aug or args.guard:
+        res = (_adam_table if args.adam_table else _dp_one_rank if args.dp_one_rank else _aug if args.aug else _guard)(args)
         print(json.dumps(res), flush=True)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
