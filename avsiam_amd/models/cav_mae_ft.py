@@ -22,6 +22,10 @@ arena layout (comm.FixedScheduleReducer), the union of the ranks' live gradient 
 and ONE avs_adam_table launch over the whole trainable arena steps exactly those classes - rates, step counts and liveness in device
 memory, no host sync.  ``.grad`` stays None after such a step and the autograd path raises.  No run with more than one rank on RCCL exists:
 verified are the arithmetic and the schedule (tests/test_ft_dp_*.py), not the scaling.
+Gradient accumulation (``set_grad_accumulation(k)``; the fused step only - the autograd path keeps refusing it): every train_step is a
+micro-step whose gradients avs_grad_accum adds into an fp32 buffer over the trainable range, the union of the gradient classes the
+micro-steps reached is kept on the device, and the k-th micro-step (or ``apply_accumulated``) takes ONE optimizer step over that union with
+the gradients divided by the micro-steps (and the ranks).
 There is no CPU/eager fallback: ``forward`` without a GPU and libavsiam_hip.so raises.
 """
 import math
@@ -169,6 +173,9 @@ class CAVMAEFT_BASE(nn.Module):
         self._guard_max = None                                     # set_grad_guard: max_norm of the guarded step; None: no guard
         self._guard = None                                         # ops.GradGuard: the guard's device block (made at the first guarded step)
         self._rates = None                                         # (base, head, mm) learning rates of the last Adam step
+        self._accum_k = None                                       # set_grad_accumulation: micro-steps per optimizer step; None: no accumulation
+        self._acc = None                                           # the accumulation buffer, its device block and the pending count (_micro_step)
+        self._guard_scale = None                                   # grad_scale of the last segment-table step (guard_stats)
         self._aug_seed = None                                      # set_aug_seed; None: derived from torch's seed at the first draw
         self._aug_st = None                                        # ops.FtAugState: the augmentation draws' key and counter, on the device
         self._aug_plans = {}                                       # batch -> the ops.FtAug buffer draw_aug draws into
@@ -198,6 +205,7 @@ class CAVMAEFT_BASE(nn.Module):
             self._opt = None
             self._dps = None
             self._guard = None
+            self._acc = None
             self._aug_st, self._aug_plans = None, {}
             self._shadow_dirty = True
         return self
@@ -335,6 +343,7 @@ class CAVMAEFT_BASE(nn.Module):
         Gradient accumulation across backwards is refused: the arena holds ONE backward's gradients, so every .grad must have been cleared
         (set to None, torch's default zero_grad) since the last one - a backward would otherwise overwrite the gradients still delivered."""
         eng.check(token)
+        self._check_not_accumulating("backward")
         held = [n for n, p in self._params.items() if p.grad is not None]
         if held:
             raise RuntimeError(f"CAVMAEFT_BASE: {len(held)} parameter(s) (e.g. {held[0]}) still hold .grad from an earlier backward; gradient "
@@ -407,6 +416,9 @@ class CAVMAEFT_BASE(nn.Module):
         rows, out = eng.loss_buf
         ops.cls_loss(x, y, n, self.label_dim, ops.CLS_BCE if loss == "BCE" else ops.CLS_CE, rows, out, dx=head.dlog)
         gmax = self._guard_max if guard is None else self._check_max_norm(guard)
+        if self._accum_k is not None:
+            self._micro_step(eng, cls_mode if mode != "mm_grad" else "mm_grad", bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, gmax)
+            return out.clone()
         if self._dp or gmax is not None:
             self._dp_step(eng, cls_mode if mode != "mm_grad" else "mm_grad", bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, gmax)
             return out.clone()
@@ -421,6 +433,7 @@ class CAVMAEFT_BASE(nn.Module):
         per gradient class (grad_class), one launch per contiguous run of the arena."""
         from .. import ops
         a = self.arena
+        self._check_not_accumulating("adam_step")
         if names is None:
             names = [n for n in self._trainable() if self._params[n].grad is not None and a.info[n].live]
         if not names:
@@ -462,6 +475,7 @@ class CAVMAEFT_BASE(nn.Module):
         Step counts of data-parallel steps already taken move back to the host, so a second call (another comm) or a return to the
         single-process adam_step continues from them."""
         from ..comm import default_comm
+        self._check_not_accumulating("set_distributed")
         self._world, self._rank = world, rank
         self._comm = comm if comm is not None else default_comm(world)
         assert self._comm.world == world and self._comm.rank == rank, "comm does not match (world, rank)"
@@ -491,7 +505,7 @@ class CAVMAEFT_BASE(nn.Module):
         train_step issues the calls it issued before.  The counters of guard_stats() start at the first guarded step."""
         if max_norm is None:
             self._guard_max = None
-            if not self._dp:
+            if not self._dp and self._accum_k is None:         # (accumulating steps stay on the segment-table route, counts on the device)
                 self._drop_dp_state()
             return
         self._guard_max = self._check_max_norm(max_norm)
@@ -505,7 +519,7 @@ class CAVMAEFT_BASE(nn.Module):
         if self._guard is None:
             return None
         r = self._guard.read()
-        scale = 1.0 / self._world if self._dp else 1.0
+        scale = self._guard_scale if self._guard_scale is not None else (1.0 / self._world if self._dp else 1.0)   # (accumulated: 1 / (j * world))
         out = {"norm": r["norm"], "coef": r["coef"], "n_nonfinite": r["n_nonfinite"], "skipped": bool(r["skip"]), "n_skipped": r["n_skipped"],
                "n_steps": r["n_steps"]}
         for i, grp in enumerate(GROUPS):
@@ -586,10 +600,17 @@ class CAVMAEFT_BASE(nn.Module):
         """Backward with the fixed-schedule all-reduce, liveness as its last message, and the one-launch Adam.  No host synchronisation.
         max_norm (a guarded step): avs_grad_sumsq over the summed gradients, then the guarded Adam.  Without an active comm (one rank,
         guarded) there is no reducer: the same table, liveness set from the classes this branch reaches."""
-        from .. import ops
-        from ..comm import _union
         a = self.arena
         lo0, hi0 = a.range[1]
+        st = self._dp_gradients(eng, cls_mode, bit)
+        self._dp_apply(st, a.g[lo0:hi0], 1.0 / self._world if st["reducer"] is not None else 1.0, lr, head_lr, mm_lr, beta1, beta2, eps,
+                       weight_decay, max_norm)
+
+    def _dp_gradients(self, eng, cls_mode, bit):
+        """The gradient half of the segment-table step: the zero-fill, the backward (with the reducer when a comm is active) and ctl.live of
+        this step - the union over the ranks once the reducer has finished.  -> the step's device state (_dp_state)."""
+        from .. import ops
+        a = self.arena
         st = self._dp_state()
         ctl, red = st["ctl"], st["reducer"]
         reach = live_classes(cls_mode, bit)
@@ -609,25 +630,129 @@ class CAVMAEFT_BASE(nn.Module):
         ctl.live.copy_(st["livevec"][cls])
         if red is not None:
             red.finish()
+        return st
+
+    def _dp_apply(self, st, g, scale, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, max_norm):
+        """The optimizer half: the rates, the (guarded) one-launch Adam over the classes live in ctl with the gradients `g` (the arena's
+        trainable range, or the accumulation buffer) scaled by `scale`, then the refreshes every step ends with."""
+        from .. import ops
+        a = self.arena
+        lo0, hi0 = a.range[1]
+        ctl = st["ctl"]
         self._rates = (lr, lr * head_lr, lr * mm_lr)
-        scale = 1.0 / self._world if red is not None else 1.0
+        self._guard_scale = scale
         if st["table"] is not None:
             ctl.set_lr(*self._rates)
             m, v = self._opt["m"], self._opt["v"]
             if max_norm is None:
-                ops.adam_table(a.p[lo0:hi0], a.g[lo0:hi0], m, v, a.pb[lo0:hi0], st["table"], ctl, beta1, beta2, eps, weight_decay,
+                ops.adam_table(a.p[lo0:hi0], g, m, v, a.pb[lo0:hi0], st["table"], ctl, beta1, beta2, eps, weight_decay,
                                grad_scale=scale)
             else:
                 if self._guard is None:
                     self._guard = ops.GradGuard(a.p.device)
-                ops.grad_sumsq(a.g[lo0:hi0], st["table"], ctl, self._guard, grad_scale=scale, max_norm=max_norm)
-                ops.adam_table_guarded(a.p[lo0:hi0], a.g[lo0:hi0], m, v, a.pb[lo0:hi0], st["table"], ctl, self._guard, beta1, beta2, eps,
+                ops.grad_sumsq(g, st["table"], ctl, self._guard, grad_scale=scale, max_norm=max_norm)
+                ops.adam_table_guarded(a.p[lo0:hi0], g, m, v, a.pb[lo0:hi0], st["table"], ctl, self._guard, beta1, beta2, eps,
                                        weight_decay, grad_scale=scale)
         a.refresh_shadows(None, cast=False)
         for e in list(self._engines.values()) + list(self._train_engines.values()):
             e.refresh_heads()
         if a.with_grads:
             self._versions = sum(p._version for p in self._params.values())
+
+    # ---- gradient accumulation over micro-batches ---------------------------------------------------------------------------------
+    def set_grad_accumulation(self, k):
+        """k >= 2: every train_step from now on is a MICRO-step; the k-th applies the sum of the k gradients, divided by k (and by the world
+        size), in one optimizer step - the step a batch k times as large would take, for a model whose activations bound the batch.  1 or
+        None: no accumulation; the buffer is freed and train_step issues the calls it issued before.
+        A micro-step takes the segment-table route of the guarded and data-parallel steps (``.grad`` stays None, the step counts live on
+        the device): the zero-fill, the backward - with the all-reduce when a comm is active, every micro-step, as DistributedDataParallel
+        does outside no_sync -, then avs_grad_accum from the gradient arena into an fp32 buffer over the trainable range (allocated at the
+        first micro-step).  Which gradient classes the cycle reached is kept on the device: under mm_grad every micro-step may run another
+        branch, and data parallel the set is the union over the ranks.  Micro-steps 1 .. k-1 launch nothing else - no Adam, no shadow or
+        head refresh; weights, moments, shadows and step counts keep their bytes.  The k-th runs the (guarded) one-launch Adam over the
+        union with ITS lr, head_lr, mm_lr, betas, eps, weight_decay and guard; every class of the union steps once.  Guarded, the norm is
+        that of the averaged gradients, n_steps counts optimizer steps, and a non-finite gradient in ANY micro-step (inf and NaN survive
+        the sum) skips the whole accumulated step.
+        Every micro-step returns its own loss, the mean of its micro-batch; all micro-steps weigh 1 / k whatever their sizes.
+        While micro-steps are pending this call, a change of the trainable set, adam_step, a backward of the autograd path,
+        load_optimizer_state and set_distributed raise RuntimeError: apply_accumulated() first.  optimizer_state() does not hold a pending
+        cycle - take checkpoints at cycle boundaries (the loop's epoch-end apply_accumulated guarantees one)."""
+        self._check_not_accumulating("set_grad_accumulation")
+        if k is None or (k == 1 and isinstance(k, int) and not isinstance(k, bool)):
+            self._accum_k, self._acc = None, None
+            if not self._dp and self._guard_max is None:
+                self._drop_dp_state()
+            return
+        if isinstance(k, bool) or not isinstance(k, int) or k < 2:
+            raise ValueError(f"set_grad_accumulation: k must be an integer >= 2 (1 or None: no accumulation), not {k!r}")
+        self._accum_k = k
+
+    def accum_state(self):
+        """{"k": micro-steps per optimizer step (1: no accumulation), "pending": micro-steps accumulated and not yet applied}: host integers,
+        no sync."""
+        return {"k": self._accum_k or 1, "pending": self._acc["pending"] if self._acc is not None else 0}
+
+    def accum_buffer(self):
+        """The fp32 accumulation buffer over the trainable range (the offsets of the Adam moments), for tests and diagnostics; None before
+        the first micro-step.  Meaningful on the segments of the classes the running cycle has reached; elsewhere it holds stale sums."""
+        return self._acc["buf"] if self._acc is not None else None
+
+    def _check_not_accumulating(self, what):
+        if self._acc is not None and self._acc["pending"]:
+            raise RuntimeError(f"CAVMAEFT_BASE.{what}: {self._acc['pending']} micro-step(s) of a gradient-accumulation cycle are pending; "
+                               "apply them first (apply_accumulated)")
+
+    def requires_grad_(self, requires_grad=True):
+        self._check_not_accumulating("requires_grad_")
+        return super().requires_grad_(requires_grad)
+
+    def _accum_check_trainable(self, what):
+        if self._acc is not None and self._acc["pending"] and self._acc["trainable"] != tuple(self._trainable()):
+            raise RuntimeError(f"CAVMAEFT_BASE.{what}: the trainable set changed while {self._acc['pending']} micro-step(s) of a gradient-"
+                               "accumulation cycle are pending; restore it and apply them first (apply_accumulated)")
+
+    def _micro_step(self, eng, cls_mode, bit, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, max_norm):
+        """One micro-step of a cycle of self._accum_k: the gradients of the segment-table route, accumulated; the k-th applies the cycle."""
+        from .. import ops
+        a = self.arena
+        lo0, hi0 = a.range[1]
+        self._accum_check_trainable("train_step")
+        st = self._dp_gradients(eng, cls_mode, bit)
+        if self._acc is None:
+            self._acc = {"buf": torch.zeros(hi0 - lo0, dtype=torch.float32, device=a.p.device), "actl": ops.GradAccumCtl(a.p.device), "pending": 0,
+                         "trainable": None}
+        acc = self._acc
+        first, last = acc["pending"] == 0, acc["pending"] + 1 >= self._accum_k
+        if first:
+            acc["trainable"] = st["trainable"]
+        if st["table"] is not None:
+            ops.grad_accum(acc["buf"], a.g[lo0:hi0], st["table"], st["ctl"], acc["actl"], first, last)
+        acc["pending"] += 1
+        if last:
+            self._accum_apply(st, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, max_norm)
+
+    def _accum_apply(self, st, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, max_norm):
+        """ctl.live holds the cycle's union: one optimizer step over it with the accumulated gradients divided by the pending micro-steps
+        (and the world size) - the quotient 1 / (j * world) taken in double and rounded once, where grad_scale becomes a float"""
+        j = self._acc["pending"]
+        world = self._world if st["reducer"] is not None else 1
+        self._acc["pending"] = 0
+        self._dp_apply(st, self._acc["buf"], 1.0 / (j * world), lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, max_norm)
+
+    def apply_accumulated(self, lr, head_lr=1.0, mm_lr=1.0, beta1=0.95, beta2=0.999, eps=1e-8, weight_decay=5e-7, *, guard=None):
+        """Apply the j pending micro-steps now, as one optimizer step with the gradients divided by j (and the world size): what the loop
+        calls after the last batch of an epoch, so that no gradient crosses an epoch (or a checkpoint).  A no-op when none are pending.
+        Data parallel every rank calls it at the same point (the ranks hold the same union: it was all-reduced micro-step by micro-step).
+        guard: as in train_step."""
+        if self._acc is None or not self._acc["pending"]:
+            return
+        self._accum_check_trainable("apply_accumulated")
+        gmax = self._guard_max if guard is None else self._check_max_norm(guard)
+        st = self._dp_state()
+        actl = self._acc["actl"]
+        st["ctl"].live.copy_(actl.live)                          # what a publishing micro-step would have left: the union so far
+        actl.n_cycles.add_(1)
+        self._accum_apply(st, lr, head_lr, mm_lr, beta1, beta2, eps, weight_decay, gmax)
 
     def optimizer_steps(self):
         """{gradient class: Adam updates it has had}.  Data parallel: copied from the device (synchronises)."""
@@ -647,6 +772,7 @@ class CAVMAEFT_BASE(nn.Module):
                 "lr": torch.tensor(self._rates if self._rates is not None else (0.0, 0.0, 0.0), dtype=torch.float64)}
 
     def load_optimizer_state(self, state):
+        self._check_not_accumulating("load_optimizer_state")
         lo0, hi0 = self.arena.range[1]
         if state["m"].numel() != hi0 - lo0 or state["v"].numel() != hi0 - lo0 or state["step"].numel() != len(CLASSES):
             raise ValueError("load_optimizer_state: the state does not fit this model's trainable range / gradient classes")

@@ -1319,6 +1319,64 @@ def grad_guard_reference(g, segs, live, grad_scale=1.0, max_norm=float("inf")):
             "skip": skip, "norm64": norm64, "coef64": coef64}
 
 
+# ---- gradient accumulation over micro-batches (csrc/grad_accum.hip) ---------------------------------------------------------------------------
+class GradAccumCtl:
+    """avs_grad_accum_ctl on the device, {float live[16]; int n_micro; int n_cycles}: ONE 72-byte buffer with typed views, zeroed here.  live:
+    the gradient classes the micro-steps of the running cycle reached; n_micro: micro-steps in it; n_cycles: cycles published."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(ADAM_TABLE_NCLS + 2, dtype=F32, device=device)
+        self.live = self.buf[:ADAM_TABLE_NCLS]
+        self.n_micro = self.buf[ADAM_TABLE_NCLS:ADAM_TABLE_NCLS + 1].view(I32)
+        self.n_cycles = self.buf[ADAM_TABLE_NCLS + 1:].view(I32)
+
+    def read(self):
+        """the block as a dict of host numbers (synchronises)"""
+        import numpy as np
+        raw = self.buf.cpu().numpy()
+        i = raw[ADAM_TABLE_NCLS:].view(np.int32)
+        return {"live": raw[:ADAM_TABLE_NCLS].copy(), "n_micro": int(i[0]), "n_cycles": int(i[1])}
+
+
+def grad_accum(acc, g, table: AdamTable, ctl: AdamCtl, actl: GradAccumCtl, first, publish):
+    """One micro-step's gradients `g` into `acc` over every segment of `table` whose class is live in `ctl`: a copy when `first` is set or the
+    class has not been touched in this cycle (actl.live), one fp32 add per element otherwise; then actl.live <- the cycle's union, and with
+    `publish` ctl.live <- that union (include/avsiam_hip.h, avs_grad_accum).  acc and g share the table's element offsets and do not overlap.
+    Two launches on the current stream, no host sync."""
+    _chk(acc, F32, "grad_accum.acc"); _chk(g, F32, "grad_accum.g")
+    _chk(table.dev, U8, "grad_accum.segs"); _chk(ctl.buf, F32, "grad_accum.ctl"); _chk(actl.buf, F32, "grad_accum.actl")
+    assert acc.numel() >= table.limit and g.numel() >= table.limit and acc.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0
+    lo, hi = acc.data_ptr(), acc.data_ptr() + 4 * table.limit
+    if g.data_ptr() < hi and lo < g.data_ptr() + 4 * table.limit:
+        raise _lib.AvsiamHipError("grad_accum: acc and g overlap")
+    _call("avs_grad_accum", acc, g, table.dev, len(table.segs), table.chunks, ctl.buf, actl.buf, int(bool(first)), int(bool(publish)), _stream())
+
+
+def grad_accum_reference(acc, g, segs, live, acc_live, first):
+    """The numpy restatement of avs_grad_accum, the yardstick of its tests.  acc, g: float32 arrays; segs: [(lo, n, group, cls), ...] - a segment
+    that breaks avs_adam_table's rules owns nothing; live: per-class liveness of this micro-step (> 0: live); acc_live: the cycle's union so
+    far (ignored when `first`).  -> (the new acc - a copy; untouched outside the segments of classes live now, the bits of g where a class is
+    first touched, acc + g in fp32 elsewhere -, the new acc_live as 0.0 / 1.0 over the 16 classes, the vector a publishing call writes to
+    ctl.live: the same union)."""
+    import numpy as np
+    acc = np.array(acc, dtype=np.float32, copy=True)
+    g = np.asarray(g, dtype=np.float32)
+    now = [c < len(live) and live[c] > 0 for c in range(ADAM_TABLE_NCLS)]
+    had = [(not first) and c < len(acc_live) and acc_live[c] > 0 for c in range(ADAM_TABLE_NCLS)]
+    for lo, n, grp, cls in segs:
+        if n <= 0 or n % 4 or lo < 0 or lo % 4 or not 0 <= grp < ADAM_TABLE_NGROUP or not 0 <= cls < ADAM_TABLE_NCLS:
+            continue
+        if not now[cls]:
+            continue
+        if had[cls]:
+            with np.errstate(invalid="ignore", over="ignore"):
+                acc[lo:lo + n] = acc[lo:lo + n] + g[lo:lo + n]
+        else:
+            acc[lo:lo + n] = g[lo:lo + n]
+    union = np.array([1.0 if (h or w) else 0.0 for h, w in zip(had, now)], dtype=np.float32)
+    return acc, union, union.copy()
+
+
 # ---- retrieval evaluation -------------------------------------------------------------------------------------------------------------
 RETRIEVAL_MAX_TOPK = 16
 _retr_ws = {}            # (device, stream) -> cached workspace: calls on different streams never share one; grown when a call needs more, so no

@@ -38,6 +38,10 @@ is the arithmetic and the message schedule (gloo ranks sharing one GPU), not the
 coefficient and the reference's skip of a step with inf / NaN gradients (GradScaler.step, traintest_ft_base.py:162-165), all on the device
 between the gradient all-reduce and Adam; the print steps add the norm, the coefficient and the steps skipped, and a run that skips more
 than half of its steps between two prints ends with "training diverged...".
+--accum-steps K: gradient accumulation (CAVMAEFT_BASE.set_grad_accumulation) - the effective batch the reference's recipes reach through
+several GPUs, on one: every batch is a micro-step whose gradients are summed on the device, every K-th batch takes the optimizer step over
+their mean, and what is pending after the last batch of an epoch is applied there.  The printed step keeps counting batches; the guard's
+counters count optimizer steps.
 --pretrain_path <dir>/best_audio_model.pth also restores <dir>/best_optim_state.pth (Adam moments, per-class steps) when it is there and
 is a fine-tuning state of this model; the pre-training loop's file of the same name (torch.optim.Adam's format) is left alone.
 """
@@ -125,6 +129,9 @@ def build_parser():
     p.add_argument('--skip-nonfinite', dest="skip_nonfinite", action="store_true",
                    help="skip steps whose gradients hold inf or NaN, without clipping (what the reference's GradScaler.step does, "
                         "traintest_ft_base.py:162-165)")
+    p.add_argument('--accum-steps', dest="accum_steps", type=int, default=1, metavar="K",
+                   help="gradient accumulation: every K batches take ONE optimizer step over the mean of their gradients, summed on the device "
+                        "(CAVMAEFT_BASE.set_grad_accumulation); what is left at the end of an epoch is applied there")
     return p
 
 
@@ -201,6 +208,8 @@ def main(argv=None):
                          "pass one of them")
     if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
         raise SystemExit(f"--clip-grad-norm {args.clip_grad_norm}: a total gradient norm > 0")
+    if args.accum_steps < 1:
+        raise SystemExit(f"--accum-steps {args.accum_steps}: the batches per optimizer step, an integer >= 1 (1: no accumulation)")
     if args.wave_input and not 0.0 <= args.mixup <= 1.0:
         raise SystemExit(f"--mixup {args.mixup}: a probability")
     if args.frame_size is not None:

@@ -71,6 +71,15 @@ def guard_diverged(steps, skipped):
     return steps > 0 and 2 * skipped > steps
 
 
+def accum_steps_of(args):
+    """-> the batches per optimizer step the launcher's --accum-steps asks for (absent: 1, no accumulation)"""
+    k = getattr(args, "accum_steps", 1)
+    k = 1 if k is None else k
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise SystemExit(f"--accum-steps {k}: the batches per optimizer step, an integer >= 1 (1: no accumulation)")
+    return k
+
+
 def input_xf_of(args):
     """the raw-input transforms of a run (args.raw_input): (InputXf.audio(dataset_mean, dataset_std), InputXf.frames()), else None"""
     if not getattr(args, "raw_input", False):
@@ -381,7 +390,11 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
     per-step augmentation of the training batches), raw_input with dataset_mean / dataset_std; optional clip_grad_norm (a max_norm) and
     skip_nonfinite: the guarded step (CAVMAEFT_BASE.set_grad_guard) - at print steps, where the loss is read anyway, the gradient norm, the
     clipping coefficient and the steps skipped so far are printed too, and a run that skipped more than half of the steps since the last
-    print ends with the reference's "training diverged..." (:184-186; there a NaN loss average) and "diverged": True in the result."""
+    print ends with the reference's "training diverged..." (:184-186; there a NaN loss average) and "diverged": True in the result.
+    Optional accum_steps K > 1 (CAVMAEFT_BASE.set_grad_accumulation): every batch is a micro-step, every K-th takes the optimizer step, and
+    what is pending after the last batch of an epoch is applied there with the epoch's rates - validation, the checkpoint and the next
+    epoch's rates all meet a cycle boundary.  global_step keeps counting batches, as the reference's loop does; the guard's counters (and
+    so the "diverged" rule) count optimizer steps."""
     max_norm = guard_max_norm(args)
     if max_norm is not None:
         audio_model.set_grad_guard(max_norm)
@@ -395,6 +408,9 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
     if master:
         os.makedirs(os.path.join(exp_dir, "models"), exist_ok=True)
     apply_freeze_base(audio_model, bool(getattr(args, "freeze_base", False)))
+    accum = accum_steps_of(args)
+    if accum > 1:
+        audio_model.set_grad_accumulation(accum)
     mm_lr = args.mm_lr if getattr(args, "mm_lr", None) is not None else args.head_lr
     hold = _LrHolder(args.lr, args.head_lr, mm_lr)
     if getattr(args, "lr_adapt", False):
@@ -435,6 +451,8 @@ def train(audio_model, train_loader, test_loader, test_sampler, args):
                         say("training diverged...", flush=True)
                         return {"best_epoch": best_epoch, "best_mAP": best_mAP, "best_acc": best_acc, "result": result, "diverged": True}
                     seen_steps, seen_skipped = gs["n_steps"], gs["n_skipped"]
+        if accum > 1:                                      # no gradient crosses the epoch (validation, the checkpoint, a new rate): a cycle boundary
+            audio_model.apply_accumulated(base_lr, head_lr=head_lr, mm_lr=mm_ratio)
         train_loss = float(torch.stack(losses).mean()) if losses else float("nan")
         stats, valid_loss = validate(audio_model, test_loader, test_sampler, args)
         mAP = float(np.nanmean([s["AP"] for s in stats]))

@@ -654,6 +654,31 @@ int avs_adam_table_guarded(float* p, const float* g, float* m, float* v, avs_bf1
                            long long n_chunks, avs_adam_ctl* ctl, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                            const avs_grad_guard* guard, avs_stream_t stream);
 
+/* ---- gradient accumulation over micro-batches (csrc/grad_accum.hip): acc (+)= g over the table and control block of avs_adam_table, and the
+ * union of the gradient classes the micro-steps of a cycle reached - on the device, where alone that set is known (data parallel: the
+ * all-reduced ctl->live; mm_grad: a branch per micro-step).  The table rules are avs_adam_table's, the geometry avs_adam_table_sized's:
+ * malformed segments own nothing, gaps belong to nobody, a chunk of a class with ctl->live[c] <= 0 is skipped before any of its memory is
+ * touched.  acc and g share the table's element offsets; 16-byte aligned.
+ *  kernel 1  for a chunk of a class that is live now:
+ *              first != 0, or actl->live[c] <= 0 (the class's first touch in this cycle):  acc = g, a copy - -0.0 and every bit survive, so
+ *                        acc never needs a zero-fill and a cycle of one micro-step hands Adam the bytes of g
+ *              otherwise:  acc = acc + g, one fp32 add per element; inf and NaN propagate by the add (what lets avs_grad_sumsq skip a whole
+ *                        accumulated step)
+ *            16-byte loads and stores, one writer per element, no atomics: two call sequences give identical bytes.
+ *  kernel 2  one workgroup, behind the first in stream order (the first reads both blocks).  For the 16 classes, with
+ *            had = first == 0 && actl->live[c] > 0 and now = ctl->live[c] > 0:  actl->live[c] = (had || now) ? 1 : 0;
+ *            n_micro = first ? 1 : n_micro + 1; with publish != 0 additionally ctl->live[c] = actl->live[c] and n_cycles += 1 - the
+ *            avs_grad_sumsq / avs_adam_table that follow see the union of the cycle.  ctl->lr and ctl->step are never written.
+ * Zero the block once, before its first use.  NULL acc / g / segs / ctl / actl, acc == g, n_segs outside 1..4096, n_chunks < 1 (or a
+ * misaligned acc / g): -2 before any launch. */
+typedef struct avs_grad_accum_ctl {
+    float live[16];
+    int n_micro;
+    int n_cycles;
+} avs_grad_accum_ctl;
+int avs_grad_accum(float* acc, const float* g, const avs_adam_seg* segs, int n_segs, long long n_chunks, avs_adam_ctl* ctl,
+                   avs_grad_accum_ctl* actl, int first, int publish, avs_stream_t stream);
+
 /* ---- Exact-fp32 forward (csrc/exact.hip; engine_exact.py): the inference forms of the fine-tuned model with fp32 operands on the f32-input
  * MFMA.  No atomics, no split-K, no shape-dependent accumulation order, no fast-math intrinsics: an output row depends on nothing but its own
  * inputs, and two calls give the same bytes.

@@ -30,6 +30,14 @@ element; the Adam phase guarded (grad_sumsq + adam_table_guarded) against unguar
 so the coefficient is in play) against plain.  Seven rounds, the ways interleaved inside a round; median and min - max of the rounds.
     python tools/bench_ft_train.py --guard --plain-only --tree <checkout of another commit, built> [--label parent]
 the plain step alone with the package of another tree: run it alternately with `--guard --plain-only` of this one.
+
+    python tools/bench_ft_train.py --accum [--out profiles/rNN/grad_accum_bench.json]
+gradient accumulation (set_grad_accumulation): avs_grad_accum alone in its copy and add forms, on the table of a mm step and with only the
+v branch's classes live, as a fraction of the float4-copy rate on 8 / 12 B per element; beside it one dense acc.add_(g) over the whole
+trainable range and the acc.zero_() a cycle would need; k = 4 micro-steps of batch 16 against four plain steps of batch 16 (mm, and the
+50 / 25 / 25 mix).  Seven rounds, the ways interleaved inside a round; median and min - max of the rounds.
+    python tools/bench_ft_train.py --accum --plain-only [--tree <checkout of another commit, built>] [--label parent]
+the plain mm step alone (--batches), with this package or another tree's: run the two alternately.
 """
 import argparse
 import json
@@ -248,6 +256,106 @@ def _guard(args):
     return res
 
 
+def _accum(args):
+    """(a) avs_grad_accum alone, copy form and add form, on the table of the mm step and on the table with only the v branch's classes live,
+    against the float4-copy rate on 8 B (copy) / 12 B (add) per element; (b) the composition one would otherwise write: one dense
+    acc.add_(g) over the whole trainable range plus the acc.zero_() a cycle needs; (c) k = 4 micro-steps of batch 16 against four plain
+    steps of batch 16, mm and the 50/25/25 mix.  --plain-only: the plain mm step alone (batches from --batches), for the parent comparison."""
+    from avsiam_amd.config import AVSiamConfig
+    from avsiam_amd.models import CAVMAEFT_BASE
+    from avsiam_amd.traintest_ft_base import SyntheticFtLoader, apply_freeze_base, draw_branch
+    import avsiam_amd
+    cfg, L = AVSiamConfig(), 527
+    kw = dict(head_lr=100.0, mm_lr=100.0)
+    res = {"metric": "ft_grad_accum", "label": args.label, "package": os.path.dirname(os.path.abspath(avsiam_amd.__file__)),
+           "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "rounds": GUARD_ROUNDS, "results": {}}
+    if args.plain_only:
+        for B in [int(b) for b in args.batches.split(",")]:
+            plain = CAVMAEFT_BASE(L).cuda()
+            apply_freeze_base(plain, False)
+            ld = SyntheticFtLoader(cfg, B, 1, L, plain.arena.p.device)
+            t = [_time(lambda i: plain.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch="mm", **kw), args.steps, args.warmup)
+                 for _ in range(GUARD_ROUNDS)]
+            res["results"][f"batch_{B}"] = {"plain_ms": _med(t)}
+            del plain
+            torch.cuda.empty_cache()
+        return res
+    from avsiam_amd import ops
+    from avsiam_amd.models.cav_mae_ft import CLASSES, live_classes
+    from avsiam_amd.ft_train import OUT, OUT_V
+    K, B = 4, 16
+    m = CAVMAEFT_BASE(L).cuda()
+    apply_freeze_base(m, False)
+    ld = SyntheticFtLoader(cfg, B, 1, L, m.arena.p.device)
+    m.set_grad_accumulation(K)
+    m.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch="mm", **kw)                  # builds the table; a mm step's gradients in the arena
+    a, st = m.arena, m._dps
+    lo0, hi0 = a.range[1]
+    table, g = st["table"], a.g[lo0:hi0]
+    acc = torch.zeros(hi0 - lo0, device=g.device)
+    actl = ops.GradAccumCtl(g.device)
+    ctls, n_live = {}, {}
+    for name, reach in (("mm", live_classes("mm_grad", OUT)), ("v", live_classes("videoonly", OUT_V))):
+        ctls[name] = ops.AdamCtl(g.device)
+        ctls[name].live[:len(CLASSES)] = torch.tensor([1.0 if c in reach else 0.0 for c in CLASSES])
+        n_live[name] = int(sum(n for _, n, _, c in table.segs if CLASSES[c] in reach))
+    for name in ("mm", "v"):                                            # every class touched once, so that the add form adds
+        ops.grad_accum(acc, g, table, ctls[name], actl, name == "mm", False)
+    ways = {}
+    for name in ("mm", "v"):
+        ways[f"kernel_copy_{name}"] = lambda i, c=ctls[name]: ops.grad_accum(acc, g, table, c, actl, True, False)
+        ways[f"kernel_add_{name}"] = lambda i, c=ctls[name]: ops.grad_accum(acc, g, table, c, actl, False, False)
+    ways["dense_add"] = lambda i: acc.add_(g)
+    ways["dense_zero"] = lambda i: acc.zero_()
+    t = {k: [] for k in ways}
+    for _ in range(GUARD_ROUNDS):
+        for k, fn in ways.items():
+            t[k].append(_time(fn, args.steps * 20, args.warmup))         # (short launches: a window of 20 x steps calls)
+    r = {k: _med(x) for k, x in t.items()}
+    n_all = hi0 - lo0
+    for name in ("mm", "v"):
+        for form, nbytes in (("copy", 8.0), ("add", 12.0)):
+            us = r[f"kernel_{form}_{name}"]["median"] * 1e3
+            r[f"kernel_{form}_{name}"].update(elements_live=n_live[name], median_us=round(us, 2),
+                                               floor_us_derived=round(nbytes * n_live[name] / COPY_RATE * 1e6, 2),
+                                               fraction_of_copy_rate=round(nbytes * n_live[name] / (us * 1e-6) / COPY_RATE, 4))
+    add_us, zero_us = r["dense_add"]["median"] * 1e3, r["dense_zero"]["median"] * 1e3
+    r["dense_add"].update(elements=n_all, median_us=round(add_us, 2), fraction_of_copy_rate=round(12.0 * n_all / (add_us * 1e-6) / COPY_RATE, 4))
+    r["dense_zero"].update(elements=n_all, median_us=round(zero_us, 2))
+    # per micro-step of a cycle of K: the kernel does one copy and K - 1 adds; the composition one zero-fill and K dense adds
+    for name in ("mm", "v"):
+        kern = (r[f"kernel_copy_{name}"]["median"] + (K - 1) * r[f"kernel_add_{name}"]["median"]) / K * 1e3
+        dense = (zero_us + K * add_us) / K
+        r[f"per_micro_step_us_{name}"] = {"kernel": round(kern, 2), "dense_add_plus_zero": round(dense, 2), "kernel_over_dense": round(kern / dense, 4)}
+    r["table"] = {"segments": len(table.segs), "chunks": table.chunks, "trainable_elements": n_all}
+    res["results"]["kernel"] = r
+    # (c) whole steps: k = 4 micro-steps of batch 16 against four plain steps of batch 16
+    m.apply_accumulated(1e-4, **kw)
+    plain = CAVMAEFT_BASE(L).cuda()
+    apply_freeze_base(plain, False)
+    rng = random.Random(0)
+    n_calls = K * (args.steps + args.warmup)
+    mix = [draw_branch(rng.uniform(0, 1)) for _ in range(n_calls)]
+    step_ways = {}
+    for sched, br in (("mm", lambda j: "mm"), ("mix_50_25_25", lambda j: mix[j % n_calls])):
+        for label, mod in (("plain", plain), ("accum", m)):
+            def cycle(i, mod=mod, br=br):
+                for j in range(K):
+                    mod.train_step(ld.a, ld.v, ld.y, 1e-4, "mm_grad", branch=br(i * K + j), **kw)
+            step_ways[f"{sched}.{label}"] = cycle
+    t = {k: [] for k in step_ways}
+    for _ in range(GUARD_ROUNDS):
+        for k, fn in step_ways.items():
+            t[k].append(_time(fn, args.steps, args.warmup) / K)          # ms per (micro-)step
+    s = {k: _med(x) for k, x in t.items()}
+    for sched in ("mm", "mix_50_25_25"):
+        p_ms, a_ms = s[f"{sched}.plain"]["median"], s[f"{sched}.accum"]["median"]
+        s[f"{sched}.summary"] = {"plain_ms_per_step": p_ms, "accum_ms_per_micro_step": a_ms, "saved_ms_per_micro_step": round(p_ms - a_ms, 4),
+                                 "samples_per_s_plain": round(B * 1e3 / p_ms, 2), "samples_per_s_accum": round(B * 1e3 / a_ms, 2)}
+    res["results"][f"k{K}_batch_{B}"] = s
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -257,17 +365,18 @@ def main(argv=None):
     ap.add_argument("--dp-one-rank", dest="dp_one_rank", action="store_true")
     ap.add_argument("--aug", action="store_true", help="the mm / a steps plain, with the fused augmentation and with the two-pass one")
     ap.add_argument("--guard", action="store_true", help="grad_sumsq alone, the Adam phase and the mm step guarded against plain")
-    ap.add_argument("--plain-only", dest="plain_only", action="store_true", help="with --aug / --guard: time the plain step only")
-    ap.add_argument("--tree", type=str, default=None, help="with --aug / --guard and --plain-only: import avsiam_amd from this checkout")
+    ap.add_argument("--accum", action="store_true", help="avs_grad_accum alone, against a dense add_ + zero_, and k = 4 micro-steps against plain steps")
+    ap.add_argument("--plain-only", dest="plain_only", action="store_true", help="with --aug / --guard / --accum: time the plain step only")
+    ap.add_argument("--tree", type=str, default=None, help="with --aug / --guard / --accum and --plain-only: import avsiam_amd from this checkout")
     ap.add_argument("--label", type=str, default=None, help="copied into the result")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON result to this file")
     args = ap.parse_args(argv)
     if args.tree:
-        if not ((args.aug or args.guard) and args.plain_only):
-            ap.error("--tree goes with --aug --plain-only or --guard --plain-only")
+        if not ((args.aug or args.guard or args.accum) and args.plain_only):
+            ap.error("--tree goes with --aug --plain-only, --guard --plain-only or --accum --plain-only")
         sys.path.insert(0, os.path.abspath(args.tree))
-    if args.adam_table or args.dp_one_rank or args.aug or args.guard:
-        res = (_adam_table if args.adam_table else _dp_one_rank if args.dp_one_rank else _aug if args.aug else _guard)(args)
+    if args.adam_table or args.dp_one_rank or args.aug or args.guard or args.accum:
+        res = (_adam_table if args.adam_table else _dp_one_rank if args.dp_one_rank else _aug if args.aug else _guard if args.guard else _accum)(args)
         print(json.dumps(res), flush=True)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
