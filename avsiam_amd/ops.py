@@ -1844,3 +1844,62 @@ def resample_wave(wave, rates, lengths=None, *, new_freq=16000, out=None, out_le
     _launch("resample_wave", (0.0, 4.0 * (wave.numel() + out.numel())), "avs_resample_wave", wave, B, C, stride, lengths, tab_idx, len(tabs),
             ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(geo, ctypes.c_void_p), out, out_stride, out_lengths, _stream())
     return out, out_lengths
+
+
+# ---- PCM decode (fine-tuning loader: dataloader_ft.py:272, torchaudio.load) ---------------------------------------------------------------------
+DECODE_MAX_CHANNELS, DECODE_TILE = 8, 1024                                      # csrc/decode.hip
+
+
+def decode_pcm(payload, desc, channels, stride, *, out=None, out_lengths=None):
+    """The payloads of WAV data chunks to planar fp32 channels in one launch (avs_decode_pcm, csrc/decode.hip; the specification is
+    preprocess.decode_pcm_reference, bit for bit): what torchaudio.load(normalize=True) returns for the file (dataloader_ft.py:272).
+
+    payload uint8 [B, byte_stride] on the device, byte_stride % 16 == 0: row b holds clip b's interleaved little-endian sample frames from
+    byte 0 (preprocess.parse_wav gives a file's data_offset and data_bytes).  desc [B, 2] = (format, n_frames) per clip, format one of
+    preprocess.PCM_U8 .. PCM_F64: host values (sequence, numpy, CPU tensor) are checked - a format outside 0 .. 5, or more frames than the row
+    or `stride` hold, is a ValueError - and uploaded; an int32 device tensor is taken at its word, and its n_frames is cut on the device to what
+    the two rows hold (an unknown format decodes to no frames).  channels: the channel count of EVERY clip of the call, 1 .. 8 (the loader
+    groups a batch by it); stride: the samples per channel row of the output.
+    -> (out fp32 [B, channels, stride], out_lengths int32 [B] on the device): zero from out_lengths[b] to stride; `out` / `out_lengths` given:
+    written in place.  One launch, no atomics: two calls give identical bytes.  With a device descriptor (what the loader passes) the call
+    does not synchronise with the host; host values are checked pair by pair in Python and uploaded with a blocking copy."""
+    from . import preprocess
+    _chk(payload, U8, "decode_pcm.payload", 2)
+    B, byte_stride = payload.shape
+    C, stride = int(channels), int(stride)
+    dev = payload.device
+    if B < 1 or byte_stride < 16 or byte_stride % 16 or payload.data_ptr() % 16:
+        raise _lib.AvsiamHipError(f"decode_pcm: payload {tuple(payload.shape)}: need at least one 16-byte aligned row whose length is a positive multiple of 16")
+    if not 1 <= C <= DECODE_MAX_CHANNELS:
+        raise _lib.AvsiamHipError(f"decode_pcm: {C} channels: 1 .. {DECODE_MAX_CHANNELS}")
+    if stride < 1:
+        raise _lib.AvsiamHipError(f"decode_pcm: stride = {stride}")
+    if torch.is_tensor(desc) and desc.is_cuda:
+        _chk(desc, I32, "decode_pcm.desc", 2)
+        if tuple(desc.shape) != (B, 2) or desc.device != dev:
+            raise _lib.AvsiamHipError(f"decode_pcm.desc: expected [{B}, 2] on {dev}, got {tuple(desc.shape)} on {desc.device}")
+    else:
+        h = torch.as_tensor(desc).reshape(-1).to(torch.int64)
+        if h.numel() != 2 * B:
+            raise _lib.AvsiamHipError(f"decode_pcm.desc: expected {B} (format, n_frames) pairs, got {h.numel()} values")
+        h = h.reshape(B, 2)
+        for b, (f, n) in enumerate(h.tolist()):
+            if not 0 <= f < len(preprocess.PCM_BYTES):
+                raise ValueError(f"decode_pcm.desc: clip {b}: format {f} (0 .. {len(preprocess.PCM_BYTES) - 1})")
+            if not 0 <= n <= min(stride, byte_stride // (C * preprocess.PCM_BYTES[f])):
+                raise ValueError(f"decode_pcm.desc: clip {b}: {n} {preprocess.PCM_NAMES[f]} frames of {C} channels do not fit {byte_stride} bytes / {stride} samples")
+        desc = h.to(I32).to(dev)
+    if out is None:
+        out = torch.empty((B, C, stride), dtype=F32, device=dev)
+    else:
+        _chk(out, F32, "decode_pcm.out", 3)
+        if tuple(out.shape) != (B, C, stride) or out.device != dev:
+            raise _lib.AvsiamHipError(f"decode_pcm.out: expected {(B, C, stride)} on {dev}, got {tuple(out.shape)} on {out.device}")
+    if out_lengths is None:
+        out_lengths = torch.empty(B, dtype=I32, device=dev)
+    else:
+        _chk(out_lengths, I32, "decode_pcm.out_lengths", 1)
+        if out_lengths.numel() != B or out_lengths.device != dev:
+            raise _lib.AvsiamHipError(f"decode_pcm.out_lengths: expected {B} values on {dev}, got {tuple(out_lengths.shape)} on {out_lengths.device}")
+    _launch("decode_pcm", (0.0, float(payload.numel() + 4 * out.numel())), "avs_decode_pcm", payload, byte_stride, desc, B, C, out, stride, out_lengths, _stream())
+    return out, out_lengths

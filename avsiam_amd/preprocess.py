@@ -6,7 +6,9 @@ Waveform input (the fine-tuning loader, dataloader_ft.py:277-340, 441-475): ``ka
 fbank (``ops.kaldi_fbank``, csrc/frontend.hip) - the Kaldi definition with the arguments of the reference's call, restated, not recorded:
 torchaudio was not available where this was written, so no golden from ``torchaudio.compliance.kaldi.fbank`` exists - and ``mixup_labels`` is
 the label side of mixup.  The frame side is ``ops.mix_frames``."""
+import collections
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -377,6 +379,38 @@ def _resample_ratio(orig_freq, new_freq):
     return int(orig_freq) // g, int(new_freq) // g
 
 
+_rate_problems = {}           # (orig, new) -> None or the reason
+
+
+def resample_rate_problem(orig_freq, new_freq=16000):
+    """None where ops.resample_wave takes a clip at `orig_freq`, else the reason as text - on the host, without a device: the caps that
+    ops.resample_table applies to a rate pair (csrc/resample.hip: a compact table of at most 16 384 words, an input span of at most 16 384
+    samples per tile of 1 024 outputs), so that a file loader can set such a clip aside when it parses the header."""
+    import math
+    key = (orig_freq, new_freq)
+    if key in _rate_problems:
+        return _rate_problems[key]
+    try:
+        o, n = _resample_ratio(orig_freq, new_freq)
+    except ValueError as e:
+        return str(e)
+    tile, max_span, why = 1024, 16384, None
+    width = math.ceil(6 * o / (min(o, n) * 0.99))
+    if o == n:
+        pass                                                            # (a clip at the target rate is not filtered)
+    elif n * 14 > RESAMPLE_MAX_WORDS:
+        why = f"{orig_freq} -> {new_freq} Hz has {n} filter phases: more than the resample kernel's table holds"
+    elif ((tile - 1) // n + 2) * o + 2 * width + 3 > max_span:
+        why = f"{orig_freq} -> {new_freq} Hz: the input span of {tile} outputs is over {max_span} samples"
+    else:
+        taps = resample_compact_table(resample_table_reference(orig_freq, new_freq)[0])[1].shape[1]
+        if n * ((taps | 1) + 1) > RESAMPLE_MAX_WORDS:
+            why = f"{orig_freq} -> {new_freq} Hz: {n} phases x {taps} taps: more than the resample kernel's table holds"
+    if len(_rate_problems) < 4096:
+        _rate_problems[key] = why
+    return why
+
+
 def _resample_phase(n):
     """the phase term of the table, -p / n for p = 0 .. n - 1 as torch promotes it: an int64 arange divided by an int is FLOAT32"""
     return torch.arange(0, -n, -1)[:, None, None] / n
@@ -516,3 +550,127 @@ def resample_reference(wave, rates, lengths=None, new_freq=16000):
         out[b, :m] = resample_channels(x, tab, width, o, n, m).mean(axis=0)
         out_lengths[b] = m
     return out, out_lengths
+
+
+# ---- WAV files: the container walk on the host and the specification of the PCM decode kernel (dataloader_ft.py:272: torchaudio.load) ----------
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)                 # csrc/decode.hip
+PCM_NAMES = ("U8", "S16", "S24", "S32", "F32", "F64")
+PCM_BYTES = (1, 2, 3, 4, 4, 8)
+PCM_MAX_CHANNELS = 8
+_WAVE_TAGS = {0x0002: "ADPCM", 0x0006: "A-law", 0x0007: "mu-law", 0x0011: "IMA ADPCM", 0x0031: "GSM 6.10", 0x0055: "MPEG layer 3"}
+_KSDATAFORMAT_TAIL = bytes.fromhex("000000001000800000aa00389b71")               # a sub-format GUID after its two tag bytes
+
+
+class WavInfo(collections.namedtuple("WavInfo", "format channels rate n_frames data_offset data_bytes")):
+    """parse_wav's result: format (PCM_U8 .. PCM_F64), channels, rate (Hz), n_frames (whole sample frames), data_offset (of the payload in the
+    file) and data_bytes = n_frames * channels * PCM_BYTES[format]"""
+    __slots__ = ()
+
+
+def parse_wav(src, name=None):
+    """The RIFF / WAVE container of one file on the host: `src` bytes (bytearray, memoryview, a uint8 numpy array) or a path; `name` is what an error calls the file
+    (default: the path, or '<bytes>').  -> WavInfo(format, channels, rate, n_frames, data_offset, data_bytes).
+
+    The chunks are walked as the container defines them: an odd-sized chunk is followed by a pad byte, and chunks other than 'fmt ' and 'data'
+    (LIST, fact, bext ...) may stand anywhere.  'fmt ' of 16, 18 or 40 bytes; WAVE_FORMAT_EXTENSIBLE is resolved through its sub-format GUID to
+    PCM or IEEE float.  A 'data' size of 0 or 0xFFFFFFFF (a streamed file) means the data runs to the end of the file, and a data chunk
+    that the file cuts short is floored to whole sample frames.  Refused with a ValueError naming the file and the reason: anything that is
+    not RIFF / WAVE (RIFX is big endian), a compressed coding (A-law, mu-law, ADPCM ...), a sample size outside 8 / 16 / 24 / 32 bit PCM and
+    32 / 64 bit float, more than 8 channels, and a block_align other than channels * bytes per sample."""
+    import struct
+    if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
+        buf, name = memoryview(src).cast("B"), name or "<bytes>"           # (no copy: a loader hands the whole file over)
+    else:
+        name = name or os.fspath(src)
+        with open(src, "rb") as f:
+            buf = memoryview(f.read())
+
+    def bad(reason):
+        return ValueError(f"{name}: {reason}")
+
+    if len(buf) < 12:
+        raise bad(f"not a WAV file: {len(buf)} bytes are too few for a RIFF header")
+    if buf[:4] == b"RIFX":
+        raise bad("RIFX (big-endian) files are not supported")
+    if buf[:4] != b"RIFF" or buf[8:12] != b"WAVE":
+        raise bad(f"not a RIFF / WAVE file (it starts with {bytes(buf[:4])!r} .. {bytes(buf[8:12])!r})")
+    fmt, data, pos = None, None, 12
+    while pos + 8 <= len(buf):
+        cid, size = bytes(buf[pos:pos + 4]), struct.unpack_from("<I", buf, pos + 4)[0]
+        body = pos + 8
+        if cid == b"fmt ":
+            if size < 16 or body + 16 > len(buf):
+                raise bad(f"'fmt ' chunk of {size} bytes: at least 16 are needed")
+            fmt = bytes(buf[body:body + min(size, len(buf) - body)])
+        elif cid == b"data":
+            avail = len(buf) - body
+            open_end = size in (0, 0xFFFFFFFF)
+            data = (body, avail if open_end else min(size, avail))
+            if open_end:
+                break
+        pos = body + size + (size & 1)
+    if fmt is None:
+        raise bad("no 'fmt ' chunk")
+    if data is None:
+        raise bad("no 'data' chunk")
+    tag, channels, rate, _, block_align, bits = struct.unpack_from("<HHIIHH", fmt, 0)
+    if tag == 0xFFFE:
+        if len(fmt) < 40:
+            raise bad(f"WAVE_FORMAT_EXTENSIBLE with a 'fmt ' chunk of {len(fmt)} bytes: 40 are needed")
+        if fmt[26:40] != _KSDATAFORMAT_TAIL:
+            raise bad(f"WAVE_FORMAT_EXTENSIBLE with an unknown sub-format GUID {fmt[24:40].hex()}")
+        tag = struct.unpack_from("<H", fmt, 24)[0]
+    if tag == 1:
+        code = {8: PCM_U8, 16: PCM_S16, 24: PCM_S24, 32: PCM_S32}.get(bits)
+        if code is None:
+            raise bad(f"{bits}-bit PCM: 8, 16, 24 and 32 bits are decoded")
+    elif tag == 3:
+        code = {32: PCM_F32, 64: PCM_F64}.get(bits)
+        if code is None:
+            raise bad(f"{bits}-bit IEEE float: 32 and 64 bits are decoded")
+    else:
+        raise bad(f"format tag 0x{tag:04x} ({_WAVE_TAGS.get(tag, 'not PCM or IEEE float')}): compressed audio is not decoded")
+    if not 1 <= channels <= PCM_MAX_CHANNELS:
+        raise bad(f"{channels} channels: 1 .. {PCM_MAX_CHANNELS} are supported")
+    if rate < 1:
+        raise bad("a sample rate of 0 Hz")
+    if block_align != channels * PCM_BYTES[code]:
+        raise bad(f"block_align {block_align} is not channels * bytes per sample = {channels} * {PCM_BYTES[code]}")
+    n_frames = data[1] // block_align
+    return WavInfo(code, int(channels), int(rate), int(n_frames), int(data[0]), int(n_frames * block_align))
+
+
+def decode_pcm_reference(payload, fmt, channels, n_frames=None):
+    """The specification of ``ops.decode_pcm``, bit for bit: the payload of a data chunk (bytes or a uint8 array; interleaved sample frames,
+    little endian) -> float32 [channels, n_frames], the convention of torchaudio.load(normalize=True) - written down from memory: torchaudio was
+    not available where this was written, and no recording exists to check it against.
+        U8   (x - 128) * 2^-7         S16  x * 2^-15         S24  (3 bytes, sign-extended) x * 2^-23            all exact in fp32
+        S32  float32(x), rounded to nearest even, * 2^-31 (INT_MAX gives 1.0)        F64  float32(x): one rounding each
+        F32  the bits: NaN payloads and -0.0 pass untouched
+    n_frames None: every whole frame of the payload."""
+    fmt, C = int(fmt), int(channels)
+    if not 0 <= fmt < len(PCM_BYTES) or not 1 <= C <= PCM_MAX_CHANNELS:
+        raise ValueError(f"decode_pcm: format {fmt} (0 .. 5), channels {C} (1 .. {PCM_MAX_CHANNELS})")
+    raw = np.frombuffer(payload, dtype=np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+    bps = PCM_BYTES[fmt]
+    held = raw.size // (C * bps)
+    n = held if n_frames is None else int(n_frames)
+    if not 0 <= n <= held:
+        raise ValueError(f"decode_pcm: {n} frames of {C} x {bps} bytes in a payload of {raw.size} bytes")
+    raw = raw[:n * C * bps]
+    if fmt == PCM_U8:
+        x = (raw.astype(np.int32) - 128).astype(np.float32) * np.float32(2.0 ** -7)
+    elif fmt == PCM_S16:
+        x = raw.view("<i2").astype(np.float32) * np.float32(2.0 ** -15)
+    elif fmt == PCM_S24:
+        b3 = raw.reshape(-1, 3).astype(np.int32)
+        v = b3[:, 0] | (b3[:, 1] << 8) | (b3[:, 2] << 16)
+        x = (v - ((v & 0x800000) << 1)).astype(np.float32) * np.float32(2.0 ** -23)
+    elif fmt == PCM_S32:
+        x = raw.view("<i4").astype(np.float32) * np.float32(2.0 ** -31)
+    elif fmt == PCM_F32:
+        x = raw.view("<u4").astype(np.uint32).view(np.float32)
+    else:
+        with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+            x = raw.view("<f8").astype(np.float32)
+    return np.ascontiguousarray(x.reshape(n, C).T)

@@ -3,8 +3,8 @@
     python -m avsiam_amd.run_cavmae_ft_base --model cav-mae-ft --ftmode mm_grad --n_class 527 --loss BCE --lr 1e-4 --head_lr 100 \\
         --mm_lr 100 --batch_size 8 --n_epochs 15 --pretrain_path exp/models/audio_model.20.pth --exp_dir ./ft_base ...
 
-Data flags behave as in the pre-training entry point: --data_train '' or 'synthetic' gives AudioSet-shaped synthetic clips with
-label-smoothed multi-hot labels (the json/wav/mp4 pipeline is out of scope on this path).  --pretrain_path loads a CAVMAE_BASE checkpoint
+Data flags: --data_train / --data_val '' or 'synthetic' give AudioSet-shaped synthetic clips with label-smoothed multi-hot labels; a path is
+the CAV-MAE json of a dataset of WAV files and extracted frames (see "Training from files" below; mp4 / video decoding is out of scope).  --pretrain_path loads a CAVMAE_BASE checkpoint
 (with or without the 'module.' prefix) with strict=False (:243-249).  --freqm / --timem / --noise are the reference's training augmentation
 (dataloader_ft.py:527-548: SpecAugment masks on the un-normalised fbank, normalisation, noise, time roll), drawn per step on the device and
 applied inside the audio patch gather; validation never augments.  Accepted but not implemented: --wa (weight averaging), --bal, and --mixup
@@ -16,8 +16,18 @@ uint8 frames - and the Kaldi fbank (dataloader_ft.py:325), its normalisation and
 waveforms mixed inside the fbank kernel's sample read (:308-322), frames with an independent weight (:457-458), labels as :470-475; the
 per-sample draws (mixed with probability p, lambda ~ Beta(10, 10), the frame weight) stay on the host, seeded per rank.  --freqm / --timem /
 --noise then act on the normalised fbank with fill (0 - mean) / std, which is the reference's SpecAugment -> normalise -> noise -> roll.
-Not built: wav / mp4 decoding, resampling, and choosing the partner from a dataset (the synthetic partner is the batch rolled by one).
-Refused together with --raw-input.
+The synthetic partner is the batch rolled by one.  Refused together with --raw-input.
+Training from files: --data_train FILE.json / --data_val FILE.json with --label_csv FILE.csv (dataset_ft: {"data": [{"wav", "labels", "video_id",
+"video_path"}]}, the csv index,mid,display_name, frames at video_path/frame_{k}/{video_id}.npy | .jpg | .png) replace the synthetic loader of that
+side and imply --wave-input: WAV files are parsed on the host (preprocess.parse_wav), their PCM payload is decoded on the device
+(ops.decode_pcm) and runs through resample -> fbank -> mixup as above, the frames through ops.resize_frames; the mixup partner is drawn from
+the whole dataset (dataloader_ft.py:372), the training frame from --total-frame frames (:352), validation takes the middle frame or, in the
+mm_grad test mode and for --eval-frames, all of them.  --n_class must equal the csv's classes.  One side may stay synthetic.  --num_workers
+read and parse files; every draw stays in the main process.  A worker inherits the open GPU, so the request is cut to what keeps one
+machine at 16 processes, ranks and the workers of both sides counted (dataset_ft.worker_share: one rank with one file side starts at most
+15, with two 7 each, 8 ranks 1 or none); validation workers end with every pass.  An unreadable clip is reported once, replaced by silence
+and a grey frame and counted; --strict-data raises instead.  --sample-rate / --audio-channels / --frame-size describe the synthetic side only: a
+file brings its own.  Not built: mp4 / video and compressed-audio decoding, --bal.
 --frame-size H W (only with --wave-input): the loaders keep their uint8 frames at the decoded size H x W, every batch draws a size per clip (the
 full size or a narrower crop, so one padded buffer holds clips of several sizes) and ops.resize_frames runs what the reference's loader does
 to them (dataloader_ft.py:136-139, 434-459: / 255, Resize([224, 224], BICUBIC, antialias=True), Normalize, the frame mix) in one launch; H and W
@@ -129,6 +139,10 @@ def build_parser():
     p.add_argument('--skip-nonfinite', dest="skip_nonfinite", action="store_true",
                    help="skip steps whose gradients hold inf or NaN, without clipping (what the reference's GradScaler.step does, "
                         "traintest_ft_base.py:162-165)")
+    p.add_argument('--strict-data', dest="strict_data", action="store_true",
+                   help="with a file dataset: an unreadable clip raises instead of being replaced by silence and a grey frame")
+    p.add_argument('--total-frame', dest="total_frame", type=int, default=10, metavar="F",
+                   help="with a file dataset: the frames extracted per clip, video_path/frame_0 .. frame_{F-1} (dataloader_ft.py:344-359)")
     p.add_argument('--accum-steps', dest="accum_steps", type=int, default=1, metavar="K",
                    help="gradient accumulation: every K batches take ONE optimizer step over the mean of their gradients, summed on the device "
                         "(CAVMAEFT_BASE.set_grad_accumulation); what is left at the end of an epoch is applied there")
@@ -191,14 +205,41 @@ def inert_flag_warnings(args):
     return out
 
 
+def data_plan(args):
+    """-> {"train": "file" | "synthetic", "val": ...}, checked: a json side needs --label_csv, both files must exist, and --n_class must equal
+    the classes the csv lists (SystemExit otherwise).  Any file side implies the wave path."""
+    plan = {side: "synthetic" if getattr(args, "data_" + side) in ('', 'synthetic') else "file" for side in ("train", "val")}
+    if "file" not in plan.values():
+        return plan
+    if not args.label_csv:
+        raise SystemExit("--data_train / --data_val name a dataset json: pass its --label_csv (index,mid,display_name) with it")
+    for path in [args.label_csv] + [getattr(args, "data_" + side) for side in plan if plan[side] == "file"]:
+        if not os.path.isfile(path):
+            raise SystemExit(f"{path}: no such file")
+    from .dataset_ft import make_index_dict
+    try:
+        n = len(make_index_dict(args.label_csv))
+    except (ValueError, KeyError) as e:
+        raise SystemExit(str(e))
+    if n != args.n_class:
+        raise SystemExit(f"--n_class {args.n_class} does not match --label_csv {args.label_csv}, which lists {n} classes")
+    if args.total_frame < 1:
+        raise SystemExit(f"--total-frame {args.total_frame}: the frames extracted per clip, an integer >= 1")
+    if plan["val"] == "file" and (args.ftmode_test or args.ftmode) == "mm_grad" and args.total_frame != 10:
+        raise SystemExit(f"--total-frame {args.total_frame}: the mm_grad test mode scores all frames of a validation clip and the model takes 10 "
+                         "(cav_mae_base.py:940); extract 10 frames per clip, or validate in another mode (--ftmode_test)")
+    return plan
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.world_size > 1 and not launched:
         raise SystemExit("data-parallel fine-tuning is launched through torchrun, one process per GPU (RANK / WORLD_SIZE / LOCAL_RANK in the "
                          "environment form the process group): --world_size alone starts no ranks")
-    if args.data_train not in ('', 'synthetic') or args.data_val not in ('', 'synthetic'):
-        raise SystemExit("only synthetic AudioSet-shaped data is supported on this path (see module docstring)")
+    args.data_plan = data_plan(args)
+    if "file" in args.data_plan.values():
+        args.wave_input = True                                                 # a file loader yields what the wave loaders yield
     if args.ftmode not in ("audioonly", "videoonly", "mm_grad"):
         raise SystemExit(f"--ftmode {args.ftmode}: the trainable modes are audioonly, videoonly and mm_grad")
     if args.eval_frames and (args.ftmode_test or args.ftmode) != "mm_grad":
@@ -265,24 +306,52 @@ def _run(args):
         model.set_distributed(args.world_size, args.rank, comm)
     dev = model.arena.p.device
     val_frames = 10 if (args.ftmode_test or args.ftmode) == "mm_grad" else 1          # validate() runs is_eval=True: mm_grad wants 10 frames
+    plan = getattr(args, "data_plan", {"train": "synthetic", "val": "synthetic"})
     if args.wave_input:
         from .traintest_ft_base import SyntheticWaveFtLoader
         norm = (args.dataset_mean, args.dataset_std)
         source = {} if args.sample_rate is None else dict(sample_rate=args.sample_rate, channels=args.audio_channels or 1)
-        train_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
-                                             mixup=args.mixup, norm=norm, train=True, frame_size=args.frame_size, **source)
-        val_loader = SyntheticWaveFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank,
-                                           label_smooth=args.label_smooth, frames=val_frames, norm=norm, train=False, frame_size=args.frame_size, **source)
+
+        def synthetic_train():
+            return SyntheticWaveFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
+                                         mixup=args.mixup, norm=norm, train=True, frame_size=args.frame_size, **source)
+
+        def synthetic_val():
+            return SyntheticWaveFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank,
+                                         label_smooth=args.label_smooth, frames=val_frames, norm=norm, train=False, frame_size=args.frame_size, **source)
     else:
-        train_loader = SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
-                                         raw=args.raw_input)
-        val_loader = SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank, label_smooth=args.label_smooth,
-                                       frames=val_frames, raw=args.raw_input)
+        def synthetic_train():
+            return SyntheticFtLoader(cfg, args.batch_size, args.steps_per_epoch, args.n_class, dev, seed=87 + args.rank, label_smooth=args.label_smooth,
+                                     raw=args.raw_input)
+
+        def synthetic_val():
+            return SyntheticFtLoader(cfg, args.batch_size, args.val_steps, args.n_class, dev, seed=88 + 1000 * args.rank, label_smooth=args.label_smooth,
+                                     frames=val_frames, raw=args.raw_input)
+
+    def file_loader(path, **kw):
+        from .dataset_ft import FileFtLoader, FtFileDataset, worker_share
+        # the ranks of this machine (torchrun's LOCAL_WORLD_SIZE; without it, all of them) and the file loaders of this rank share 16 processes
+        ranks = int(os.environ.get("LOCAL_WORLD_SIZE", args.world_size))
+        workers = worker_share(args.num_workers, loaders=list(plan.values()).count("file"), ranks=ranks)
+        return FileFtLoader(FtFileDataset(path, args.label_csv, args.n_class), cfg, args.batch_size, dev, label_smooth=args.label_smooth, norm=norm,
+                            total_frame=args.total_frame, num_workers=workers, rank=args.rank, world=args.world_size, strict=args.strict_data, **kw)
+
+    train_loader = file_loader(args.data_train, seed=87, mixup=args.mixup, train=True) if plan["train"] == "file" else synthetic_train()
+    val_loader = (file_loader(args.data_val, seed=88, train=False, frames="all" if val_frames > 1 else "middle") if plan["val"] == "file"
+                  else synthetic_val())
+    # data parallel: validate() truncates the gathered, padded shards of a file set to len(dataset)
+    val_sampler = val_loader.sampler if plan["val"] == "file" and args.world_size > 1 else None
     os.makedirs(args.exp_dir or ".", exist_ok=True)
     args.exp_dir = args.exp_dir or "."
-    result = train(model, train_loader, val_loader, None, args)
+    result = train(model, train_loader, val_loader, val_sampler, args)
+    for name, loader in (("training", train_loader), ("validation", val_loader)):
+        if getattr(loader, "n_bad", 0):
+            print(f"{loader.n_bad} unreadable {name} clip(s) were replaced by silence / a grey frame", flush=True)
     if args.eval_frames:
         result["frame_res"] = evaluate_frames(model, val_loader, args)
+    for loader in (train_loader, val_loader):
+        if hasattr(loader, "close"):
+            loader.close()                                                   # the training workers end here
     return result
 
 

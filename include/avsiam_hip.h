@@ -299,6 +299,19 @@ int avs_resample_plan(int o, int n, int width, int taps, int* table_words, int* 
 int avs_resample_wave(const float* wave, int B, int C, long long stride, const int* len, const int* tab_idx, int n_tables,
                       const void* const* tables, const int* geo, float* out, long long out_stride, int* out_len, avs_stream_t stream);
 
+/* ---- PCM decode (dataloader_ft.py:272: torchaudio.load, normalize=True): the payload of a WAV file's data chunk - interleaved sample frames, little
+ * endian - to the planar fp32 channels avs_resample_wave reads, in one launch.  The specification is avsiam_amd.preprocess.decode_pcm_reference
+ * (numpy, bit for bit).  payload uint8 [B, byte_stride], 16-byte aligned, byte_stride % 16 == 0: row b holds clip b's payload from byte 0 (what lies
+ * behind it is never decoded).  desc (DEVICE) int32 [B, 2] = { format, n_frames } per clip; C: the channels of every clip of the call, 1 .. 8.
+ *   format   0 U8   (x - 128) * 2^-7            exact          3 S32  (float)x (round to nearest even) * 2^-31      one rounding
+ *            1 S16  x * 2^-15                   exact          4 F32  the bits (NaN payloads, -0.0)                 exact
+ *            2 S24  3 bytes, sign-extended, x * 2^-23  exact   5 F64  (float)x (a NaN stays a NaN, its payload is not specified)  one rounding
+ *   out      fp32 [B, C, stride]: out[b, c, f] = sample c of frame f for f < out_len[b], zero from there to stride
+ *   out_len  int32 [B] (DEVICE): n_frames cut to 0 .. min(stride, byte_stride / (C * bytes per sample)); 0 for a format outside 0 .. 5
+ * One writer per cell, no atomics: two calls give identical bytes.  No synchronisation. */
+int avs_decode_pcm(const uint8_t* payload, long long byte_stride, const int* desc, int B, int C, float* out, long long stride, int* out_len,
+                   avs_stream_t stream);
+
 /* ---- decoded-size frames (dataloader_ft.py:136-139, 434-459): frames / 255, Resize([224, 224], BICUBIC, antialias=True), Normalize and the frame
  * mix, from uint8 frames at the video's own size.  The specification is avsiam_amd.preprocess.resize_frames_reference (float64): torch's
  * interpolate(mode='bicubic', align_corners=False, antialias=True), no clamping.  Per axis with input size I and output size O, in float64:
