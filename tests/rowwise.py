@@ -8,7 +8,8 @@ absolute value, so that a row whose gradient cancels is still measured against w
 
 Pure torch, no call into the library: every function runs on whatever device its inputs live on (the tests evaluate them on the
 CPU).  tests/test_rowwise_cpu.py proves on emulations that the measures accept honest rounding and reject subtle damage;
-tests/test_rowwise_gpu.py applies them to the kernels."""
+tests/test_rowwise_gpu.py applies them to the kernels.  For attention inputs whose softmax is peaked, tied or shifted (ATTN_PROFILES) the
+magnitude rows are the *_full ones (attention_measures_full): tests/test_attn_peaked_cpu.py / tests/test_attn_peaked_gpu.py."""
 import math
 
 import torch
@@ -195,7 +196,7 @@ def _rows(x):
     return x.permute(1, 0, 2).reshape(L, H * hd)
 
 
-def attention_eval(qkv, lens, H, dout, lq=0, emulate=False):
+def attention_eval(qkv, lens, H, dout, lq=0, emulate=False, mutant=None):
     """Forward and backward of every sequence, written out as formulas:
         P = softmax(scale q k^T), out = P v, lse = log sum exp (natural log of the scaled scores: what the kernels store),
         dP = dO v^T, delta = sum_d out dO, dS = P o (dP - delta), dq = scale dS k, dk = scale dS^T q, dv = P^T dO.
@@ -207,6 +208,11 @@ def attention_eval(qkv, lens, H, dout, lq=0, emulate=False):
     products, dq / dk / dv - and delta from the ROUNDED out.
     lq > 0: only the first lq rows of every sequence are queries; out / dout are compact (sequence s owns rows s * lq ..), lse / delta and
     the gradients keep the packed numbering (zeros where nothing is defined).
+    emulate=False also returns dq_full / dk_full / dv_full, the magnitude rows with every FACTOR made absolute (dS_abs takes |.| of the sums dP
+    and delta, which on a peaked row both cancel to far less than the rounding that delta carries from the bf16 out):
+    dS_full = P o (|dO| |v|^T + sum_d |out dO|), dq_full = scale dS_full |k|, dk_full = ln 2 dS_full^T |q~|, dv_full = P^T |dO| (= dv_abs).
+    mutant (emulate only; the damage of the CPU proofs, tests/test_attn_peaked_cpu.py): ("bwd_tail_key", L, h) - in the sequence of length L, head
+    h, the backward of ONE query row (the one whose score of that key is lowest) also sees key L, the following row of the packed matrix.
     -> dict of [rows, D] (out: [nq, D]) and [H, rows] tensors."""
     dt = torch.float32 if emulate else F64
     D = qkv.shape[1] // 3
@@ -216,6 +222,9 @@ def attention_eval(qkv, lens, H, dout, lq=0, emulate=False):
     dev = qkv.device
     nq = sum(min(lq, L) if lq else L for L in lens)
     res = {k: torch.zeros(nq if k.startswith("out") else rows, D, dtype=dt, device=dev) for k in ("out", "dq", "dk", "dv", "out_abs", "dq_abs", "dk_abs", "dv_abs")}
+    if not emulate:
+        for k in ("dq_full", "dk_full", "dv_full"):
+            res[k] = torch.zeros(rows, D, dtype=dt, device=dev)
     for k in ("lse", "delta", "delta_abs"):
         res[k] = torch.zeros(H, rows, dtype=dt, device=dev)
     r0 = o0 = 0
@@ -244,9 +253,20 @@ def attention_eval(qkv, lens, H, dout, lq=0, emulate=False):
         dS = P * (dP - delta.unsqueeze(-1))
         dSm = bf16_round(dS) if emulate else dS
         dq = (dSm @ k) * scale
+        if emulate and mutant is not None and mutant[0] == "bwd_tail_key" and mutant[1] == L and r0 + L < qkv.shape[0]:
+            h = mutant[2]
+            kx = qkv[r0 + L, D + h * hd:D + (h + 1) * hd].to(dt)
+            vx = qkv[r0 + L, 2 * D + h * hd:2 * D + (h + 1) * hd].to(dt)
+            sx = qt[h] @ kx
+            i = int(sx.argmin())
+            px = torch.exp2(sx[i] - lse[h, i] * LOG2E)
+            dsx = bf16_round(px * (dO[h, i] @ vx - delta[h, i]))
+            dq[h, i] = dq[h, i] + dsx * kx * scale
         dk = (dSm.transpose(1, 2) @ qt) * LN2                      # scale q = q~ ln 2
         dv = Pv.transpose(1, 2) @ dO
         if emulate:
+            for name, t, n in (("dq_raw", dq, Lq), ("dk_raw", dk, L), ("dv_raw", dv, L)):      # the fp32 values before their rounding: what an 8-bit copy is taken from
+                res.setdefault(name, torch.zeros(rows, D, dtype=dt, device=dev))[r0:r0 + n] = _rows(t)
             dq, dk, dv = bf16_round(dq), bf16_round(dk), bf16_round(dv)
         res["out"][o0:o0 + Lq] = _rows(out)
         res["dq"][r0:r0 + Lq] = _rows(dq)
@@ -261,6 +281,10 @@ def attention_eval(qkv, lens, H, dout, lq=0, emulate=False):
             res["dk_abs"][r0:r0 + L] = _rows((dSa.transpose(1, 2) @ qt.abs()) * LN2)
             res["dv_abs"][r0:r0 + L] = _rows(P.transpose(1, 2) @ dO.abs())
             res["delta_abs"][:, r0:r0 + Lq] = (out * dO).abs().sum(-1)
+            dSf = P * (dO.abs() @ v.abs().transpose(1, 2) + (out * dO).abs().sum(-1, keepdim=True))
+            res["dq_full"][r0:r0 + Lq] = _rows((dSf @ k.abs()) * scale)
+            res["dk_full"][r0:r0 + L] = _rows((dSf.transpose(1, 2) @ qt.abs()) * LN2)
+            res["dv_full"][r0:r0 + L] = res["dv_abs"][r0:r0 + L]
         r0 += L
         o0 += Lq
     return res
@@ -314,6 +338,105 @@ def attention_tolerances(emu):
         if k in emu:
             tol[k] = 3.0 * max(emu[k], U_F32)                       # (never below one fp32 rounding of a value of size 1)
     return tol
+
+
+def attention_measures_full(got, ref, H, lens, rows_mask=None, tol=None):
+    """attention_measures for inputs whose softmax is peaked or shifted: dq / dk / dv per (row, head) as
+        ||got - ref|| / max(||full||, 2^-20 max over the rows of the same (sequence, head) of ||full||)
+    with the *_full magnitude rows of attention_eval.  The floor is a condition, not a measurement: a key that receives P = 1e-60 has a true gradient
+    of that size, any fp32 evaluation returns 0 for it, and against its own magnitude that is a ratio of 1; under the floor the unit is still
+    compared - absolutely, against a quantity a million times below the largest gradient row of its own sequence and head.  out, out_rel, lse and delta
+    are measured as attention_measures measures them.  A value that is not finite counts as infinite."""
+    res = attention_measures({k: v for k, v in got.items() if k in ("out", "lse", "delta")}, ref, H, rows_mask, tol)
+    for k in ("dq", "dk", "dv"):
+        if k not in got:
+            continue
+        rows, D = ref[k].shape
+        e = (got[k].double() - ref[k].double()).reshape(rows, H, D // H).norm(dim=-1)
+        m = ref[k + "_full"].double().reshape(rows, H, D // H).norm(dim=-1)
+        floor = torch.zeros_like(m)
+        r0 = 0
+        for L in lens:
+            floor[r0:r0 + L] = m[r0:r0 + L].max(dim=0, keepdim=True).values * 2.0 ** -20
+            r0 += L
+        r = torch.where(e == 0, torch.zeros_like(e), e / torch.maximum(m, floor).clamp_min(1e-300))
+        r = torch.nan_to_num(r, nan=float("inf"))
+        if rows_mask is not None:
+            r = r[rows_mask]
+        res[k] = float(r.max()) / (tol[k] if tol is not None else 1.0)
+    return {k: (v if v == v else float("inf")) for k, v in res.items()}
+
+
+def attention_tolerances_full(emu, ref):
+    """attention_tolerances for the full measure: 3 x the emulation's worst value on the same inputs, never above the suite's whole-tensor tolerance;
+    lse never below 4 x 2^-24 max |lse| of the case - the rounding of the reference point, of the sum and of the product by ln 2, each at the
+    magnitude of lse (the offset profiles: |lse| ~ 250)"""
+    tol = attention_tolerances(emu)
+    if "lse" in tol:
+        tol["lse"] = max(tol["lse"], 4.0 * U_F32 * float(ref["lse"].abs().max()))
+    return tol
+
+
+def attention_forward_lazy(qkv, lens, H, tile=64, lazy_sum=2.0 ** 40, mutant=None):
+    """The forward kernels' walk over the key tiles (csrc/attention.hip attn_fwd_kernel / attn_fwd_ring_kernel), restated in torch fp32: the scores
+    of a tile start at -m_run; the first tile fixes the reference point m_run at its row maximum; a later tile whose row sum of p = exp2(s - m_run)
+    is not below lazy_sum moves it - scores recomputed, tail keys masked AGAIN, d = max(new row maximum, 0), the sum and the accumulated P.V scaled by
+    exp2(-d) (which underflows to 0 for d > 149) - for all 32 rows of the wave together; P is rounded to bf16 before P.V; keys beyond L are copies of
+    key L - 1 (tile_load clamps the row) and masked to -inf; lse = (m_run + log2 l) ln 2.  (The kernels test the sum of each half of a row's 64
+    keys, this the whole row's: a factor of two in a threshold of 2^40.)
+    mutant: "no_o_rescale" - the move scales the sum but not the accumulated P.V; "no_remask" - the move leaves the tail keys unmasked;
+    "lse_first_ref" - lse is saved from the first tile's reference point.
+    -> (out [rows, D] fp32 holding bf16 values, lse [H, rows], moves [H, rows]: how often the row's reference point moved)"""
+    D = qkv.shape[1] // 3
+    rows = sum(lens)
+    f = torch.float32
+    out, lse, moves = torch.zeros(rows, D, dtype=f), torch.zeros(H, rows, dtype=f), torch.zeros(H, rows, dtype=torch.int64)
+    r0 = 0
+    for L in lens:
+        x = qkv[r0:r0 + L].to(f)
+        q, k, v = _heads(x[:, :D], H), _heads(x[:, D:2 * D], H), _heads(x[:, 2 * D:], H)
+        m_run, m_first, l_run = torch.zeros(H, L), torch.zeros(H, L), torch.zeros(H, L)
+        o = torch.zeros_like(q)
+        nmove = torch.zeros(H, L, dtype=torch.int64)
+        wave = torch.arange(L) // 32
+        for k0 in range(0, L, tile):
+            idx = torch.arange(k0, k0 + tile).clamp_max(L - 1)
+            dead = torch.arange(k0, k0 + tile) >= L
+            kt, vt = k[:, idx], v[:, idx]
+            raw = q @ kt.transpose(1, 2)
+            s = (raw - m_run.unsqueeze(-1)).masked_fill(dead, float("-inf"))
+            if k0 == 0:
+                m_run = s.max(dim=-1).values
+                m_first = m_run.clone()
+                s = s - m_run.unsqueeze(-1)
+            p = torch.exp2(s)
+            psum = p.sum(-1)
+            if k0 != 0:
+                trig = ~(psum < lazy_sum)
+                hit = torch.zeros(H, int(wave.max()) + 1, dtype=torch.bool).index_put_((torch.arange(H)[:, None].expand(H, L), wave.expand(H, L)), trig, accumulate=True)
+                trig = hit[:, wave]                                 # wave-uniform: the 32 rows of a wave move together
+                if bool(trig.any()):
+                    s2 = raw - m_run.unsqueeze(-1)
+                    if mutant != "no_remask":
+                        s2 = s2.masked_fill(dead, float("-inf"))
+                    d = s2.max(dim=-1).values.clamp_min(0.0) * trig
+                    alpha = torch.exp2(-d)
+                    l_run = l_run * alpha
+                    if mutant != "no_o_rescale":
+                        o = o * alpha.unsqueeze(-1)
+                    m_run = m_run + d
+                    nmove += (d > 0).long()
+                    s2 = s2 - d.unsqueeze(-1)
+                    s = torch.where(trig.unsqueeze(-1), s2, s)
+                    p = torch.exp2(s)
+                    psum = p.sum(-1)
+            l_run = l_run + psum
+            o = o + bf16_round(p) @ vt
+        out[r0:r0 + L] = _rows(bf16_round(o / l_run.unsqueeze(-1)))
+        lse[:, r0:r0 + L] = ((m_first if mutant == "lse_first_ref" else m_run) + torch.log2(l_run)) * LN2
+        moves[:, r0:r0 + L] = nmove
+        r0 += L
+    return out, lse, moves
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -424,14 +547,65 @@ def gemm_tn_case(M, N1, N2, seed=0):
     return {"A": A, "B": B, "C0": torch.randn(N1, N2, generator=g) * 2.0}
 
 
-def attn_case(H, hd, lens, lq=0, seed=0):
-    """packed qkv (bf16, q columns pre-multiplied by hd^-0.5 log2 e as the qkv GEMM's epilogue leaves them) and dO (compact when lq)"""
+# score profiles of attn_case: what a trained model's softmax looks like and N(0, 1) draws do not (a spread of ~12 log2 units, a largest
+# probability of ~0.05).  Each acts on the unscaled q / k of every (sequence, head); u is a unit vector of that (sequence, head), j the key's
+# position in its sequence, offsets are in natural-log score units (q . k hd^-0.5).
+#   sharp            q *= 6: the mean largest P is ~0.68
+#   late_spike       keys floor(2 L / 3) and L - 3 (L - 1 when L < 3) times 8, every 7th query row times 6: scores ~70 log2 units above the rest, late
+#   staircase        q += 4 sqrt(hd) u, k_j += 11.7 floor(j / 64) u: every 64-key tile ~47 nat (68 log2 units) above the one before it
+#   offset_pos/_neg  q += 6 sqrt(hd) u, k += +-35 u: every score ~ +-210 nat (303 log2 units), |lse| ~ 210 ... 250
+#   ties             every key of a (sequence, head) equals key 0: P is exactly uniform
+#   first_tile_high  q += 4 sqrt(hd) u, k_j -= 60 u from key 64 on: everything behind the first tile underflows to p = 0
+ATTN_PROFILES = ("sharp", "late_spike", "staircase", "offset_pos", "offset_neg", "ties", "first_tile_high")
+
+
+def _apply_profile(x, profile, H, hd, lens, g):
+    """the profile's change of the unscaled q (columns [0, D)) and k (columns [D, 2 D)) of x, in place; draws come after those of attn_case"""
+    D = H * hd
+    u = torch.randn(len(lens), H, hd, generator=g)
+    u = u / u.norm(dim=-1, keepdim=True)
+    r0 = 0
+    for i, L in enumerate(lens):
+        q = x[r0:r0 + L, :D].view(L, H, hd)
+        k = x[r0:r0 + L, D:2 * D].view(L, H, hd)
+        j = torch.arange(L)
+        if profile == "sharp":
+            q *= 6.0
+        elif profile == "late_spike":
+            for kj in ((2 * L) // 3, L - 3 if L >= 3 else L - 1):
+                k[kj] *= 8.0
+            q[::7] *= 6.0
+        elif profile == "staircase":
+            q += 4.0 * math.sqrt(hd) * u[i]
+            k += 11.7 * (j // 64).float()[:, None, None] * u[i]
+        elif profile in ("offset_pos", "offset_neg"):
+            q += 6.0 * math.sqrt(hd) * u[i]
+            k += (35.0 if profile == "offset_pos" else -35.0) * u[i]
+        elif profile == "ties":
+            k[:] = k[0].clone()
+        elif profile == "first_tile_high":
+            q += 4.0 * math.sqrt(hd) * u[i]
+            k -= 60.0 * (j >= 64).float()[:, None, None] * u[i]
+        else:
+            raise ValueError(profile)
+        r0 += L
+
+
+def attn_case(H, hd, lens, lq=0, seed=0, profile=None, scaled=True):
+    """packed qkv (bf16, q columns pre-multiplied by hd^-0.5 log2 e as the qkv GEMM's epilogue leaves them) and dO (compact when lq).
+    profile: one of ATTN_PROFILES applied to the same N(0, 1) draws before the scaling and the rounding (None / "randn": the draws as they
+    are).  scaled=False: qkv stays fp32 with q unscaled (the exact-fp32 forward's operand)."""
     g = _gen(H, hd, len(lens), sum(lens), lq, seed)
     D, rows = H * hd, sum(lens)
     x = torch.randn(rows, 3 * D, generator=g)
-    x[:, :D] *= attn_q_scale(hd)
     nq = sum(min(lq, L) if lq else L for L in lens)
-    return {"qkv": x.to(torch.bfloat16), "dout": torch.randn(nq, D, generator=g).to(torch.bfloat16)}
+    dout = torch.randn(nq, D, generator=g).to(torch.bfloat16)
+    if profile not in (None, "randn"):
+        _apply_profile(x, profile, H, hd, lens, g)
+    if not scaled:
+        return {"qkv": x, "dout": dout}
+    x[:, :D] *= attn_q_scale(hd)
+    return {"qkv": x.to(torch.bfloat16), "dout": dout}
 
 
 def ln_case(D, kind, rows=33, seed=0):
