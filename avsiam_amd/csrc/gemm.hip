@@ -75,13 +75,9 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 //   1  the epilogue computes everything but issues no global store      2  no epilogue at all (accumulators kept alive)
 //   3  as 2, and every tile streams the operands of tile 0 (all operand loads hit the L2: main loop without the memory system)
 //   4  as 2, with the phase's 16 MFMAs of 16x16x32 replaced by 8 of 32x32x16 on the same registers (timing only, wrong results)
+//   5  every row step of the epilogue's addresses is zero: a lane reads and writes its first row only (wrong results, inside the allocation)
 #ifndef NT8_ABLATE
 #define NT8_ABLATE 0
-#endif
-#if NT8_ABLATE == 1
-#define NT_STORE(ptr, val) asm volatile("" ::"v"(val))
-#else
-#define NT_STORE(ptr, val) *(ptr) = (val)
 #endif
 
 __device__ __forceinline__ void epi_apply4(float alpha, int ACT, float (&v)[4], const float4& bias4, uint2 p,
@@ -114,6 +110,47 @@ __device__ __forceinline__ void epi_lds_wait() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// Epilogue addressing.  Every stream the epilogue touches (out, out2, out8, res, aux) is a row-major matrix of which a wave owns rows
+// mw0.. and 64 columns from nw0.  Per tile and stream there is ONE buffer descriptor (wave-uniform: base = first byte of the wave's
+// block, num_records = the bytes from there to the end of row M - 1) and ONE 32-bit per-lane byte offset (the lane's row quad and
+// column chunk); the row steps of the unrolled loops are wave-uniform multiples of the leading dimension added to it.  The
+// hardware's range check (offset + access size > num_records: a load returns zero, a store is dropped) stands for the row clamps
+// and row masks: a row at or behind M starts at or behind num_records, and a row in front of M ends inside it because
+// nw0 + 64 <= N <= ld.  Formed per row as (size_t)m * ld + n, clamped and masked, this bookkeeping was more than half of the
+// plain epilogue's VALU instructions.  Needs every stream's extent M x ld below 4 GiB (checked by the host).
+typedef __amdgpu_buffer_rsrc_t epi_rsrc_t;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+// (readfirstlane: the wave id comes from threadIdx, and a descriptor hipcc cannot prove uniform gets a loop around every access)
+__device__ __forceinline__ epi_rsrc_t epi_rsrc_raw(unsigned long long addr, unsigned num_records) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)addr);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(addr >> 32));
+    const unsigned rec = (unsigned)__builtin_amdgcn_readfirstlane((int)num_records);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(size_t)(((unsigned long long)hi << 32) | lo), 0, (int)rec, 0x00020000);
+}
+__device__ __forceinline__ epi_rsrc_t epi_rsrc(const void* p, unsigned ld_bytes, int mw0, unsigned col_bytes, int M) {
+    const unsigned rows = (unsigned)max(M - mw0, 0);
+    const unsigned long long addr = (unsigned long long)(size_t)p + (unsigned long long)(unsigned)mw0 * ld_bytes + col_bytes;
+    return epi_rsrc_raw(addr, p != nullptr && rows != 0 ? rows * ld_bytes - col_bytes : 0u);
+}
+// byte offset of a row step (wave-uniform; a compile-time row count times the stream's leading dimension)
+__device__ __forceinline__ unsigned epi_row_off(int rows, unsigned ld_bytes) {
+#if NT8_ABLATE == 5
+    return 0u;
+#else
+    return (unsigned)rows * ld_bytes;
+#endif
+}
+__device__ __forceinline__ void epi_store128(const u32x4& v, epi_rsrc_t r, unsigned off) {
+#if NT8_ABLATE != 1
+    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, 0);
+#else
+    asm volatile("" ::"v"(v));
+#endif
+}
+__device__ __forceinline__ void epi_store64(const u32x2& v, epi_rsrc_t r, unsigned off) {
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, 0);
+}
+
 // Operands the epilogue reads from HBM (fp32 residual rows / bf16 GELU' pre-activations) are loaded in groups that are
 // double-buffered in registers: a load in the epilogue is synchronous (its latency is paid by the one workgroup of the
 // CU), so group g+1 is in flight while group g is transposed and stored, and group 0 is issued by the caller BEFORE the
@@ -132,44 +169,53 @@ struct EpiPrefetch {
 
 template <int MI>
 __device__ __forceinline__ void epi_load_res(const GemmNtArgs& a, f32x4 (&rs)[EpiPrefetch<MI>::RG][4], int grp, int lane, int mw0, int nw0) {
-    const int n = nw0 + (lane & 15) * 4, rq = lane >> 4;
+    const unsigned cb = (lane & 15) * 16, rq = lane >> 4, ldb = (unsigned)a.ldr * 4u;
     // the row gather (res_idx) is decided ONCE, outside the loads: a per-element "index or row" select makes hipcc branch
     // around every index load and wait vmcnt(0) in front of every residual load - serialising them behind each other
     // and behind the LDS-DMAs of the next tile that are in flight during the epilogue
     if (a.res_idx) {
-        int rrow[EpiPrefetch<MI>::RG][4];
+        // the wave's slice of the index list (a row at or behind M reads index 0: its result is dropped) and the whole table from
+        // column nw0 (its height is the caller's business: no range check); per gathered row one 32-bit multiply remains
+        const epi_rsrc_t ri = epi_rsrc(a.res_idx, 4u, mw0, 0u, a.M);
+        const epi_rsrc_t rt = epi_rsrc_raw((unsigned long long)(size_t)a.res + (unsigned)nw0 * 4u, 0xffffffffu);
+        unsigned rrow[EpiPrefetch<MI>::RG][4];
 #pragma unroll
         for (int mj = 0; mj < EpiPrefetch<MI>::RG; ++mj)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rrow[mj][i] = a.res_idx[min(mw0 + (grp * EpiPrefetch<MI>::RG + mj) * 16 + i * 4 + rq, a.M - 1)];
+            for (int i = 0; i < 4; ++i)
+                rrow[mj][i] = __builtin_amdgcn_raw_buffer_load_b32(ri, (int)((rq + (grp * EpiPrefetch<MI>::RG + mj) * 16 + i * 4) * 4u), 0, 0);
 #pragma unroll
         for (int mj = 0; mj < EpiPrefetch<MI>::RG; ++mj)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rs[mj][i] = *reinterpret_cast<const f32x4*>(a.res + (long long)rrow[mj][i] * a.ldr + n);
+            for (int i = 0; i < 4; ++i)
+                rs[mj][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rt, (int)(rrow[mj][i] * ldb + cb), 0, 0));
     } else {
+        const epi_rsrc_t r = epi_rsrc(a.res, ldb, mw0, (unsigned)nw0 * 4u, a.M);
+        const unsigned off = rq * ldb + cb;
 #pragma unroll
         for (int mj = 0; mj < EpiPrefetch<MI>::RG; ++mj)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = min(mw0 + (grp * EpiPrefetch<MI>::RG + mj) * 16 + i * 4 + rq, a.M - 1);
-                rs[mj][i] = *reinterpret_cast<const f32x4*>(a.res + (long long)m * a.ldr + n);
-            }
+            for (int i = 0; i < 4; ++i)
+                rs[mj][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off + epi_row_off((grp * EpiPrefetch<MI>::RG + mj) * 16 + i * 4, ldb)), 0, 0));
     }
 }
 
 template <int MI>
 __device__ __forceinline__ void epi_load_aux(const GemmNtArgs& a, u32x4 (&ax)[EpiPrefetch<MI>::AG][2], int grp, int lane, int mw0, int nw0) {
-    const int n = nw0 + (lane & 7) * 8, rq = lane >> 3;
+    // bf16 gelu'(x): 16 bytes per lane; 8-bit codes: 8 bytes per lane, ldaux counts bytes (block-uniform)
+    const unsigned es = a.aux8 ? 1u : 2u, ldb = (unsigned)a.ldaux * es;
+    const epi_rsrc_t r = epi_rsrc(a.aux, ldb, mw0, (unsigned)nw0 * es, a.M);
+    const unsigned off = (unsigned)(lane >> 3) * ldb + (unsigned)(lane & 7) * 8u * es;
 #pragma unroll
     for (int mj = 0; mj < EpiPrefetch<MI>::AG; ++mj)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int m = min(mw0 + (grp * EpiPrefetch<MI>::AG + mj) * 16 + i * 8 + rq, a.M - 1);
-            if (a.aux8) {                                  // 8 codes = 8 bytes per lane (block-uniform branch)
-                const uint2 c = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(a.aux) + (size_t)m * a.ldaux + n);
-                ax[mj][i] = u32x4{c.x, c.y, 0u, 0u};
+            const unsigned o = off + epi_row_off((grp * EpiPrefetch<MI>::AG + mj) * 16 + i * 8, ldb);
+            if (a.aux8) {
+                const u32x2 c = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)o, 0, 0));
+                ax[mj][i] = u32x4{c[0], c[1], 0u, 0u};
             } else
-            ax[mj][i] = *reinterpret_cast<const u32x4*>(a.aux + (size_t)m * a.ldaux + n);
+            ax[mj][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)o, 0, 0));
         }
 }
 
@@ -209,7 +255,9 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
     // store -> load -> store chain over the whole epilogue.
     if (ACT == 0 && a.out_f32) {                                                   // fp32 output exists without activation only
         const int cc = (lane & 15) * 4, rq = lane >> 4;
-        const int n = nw0 + cc;
+        const unsigned ldo_b = (unsigned)a.ldo * 4u;
+        const epi_rsrc_t ro = epi_rsrc(a.out, ldo_b, mw0, (unsigned)nw0 * 4u, a.M);
+        const unsigned oo = (unsigned)rq * ldo_b + (unsigned)cc * 4u;
         float* stg = reinterpret_cast<float*>(smem) + wave * (16 * 68);
         const float* sbias = reinterpret_cast<const float*>(smem) + (blockDim.x >> 6) * (16 * 68) + wave * 64;
         constexpr int RG = EpiPrefetch<MI>::RG, NG = MI / RG, NB = EpiPrefetch<MI>::NB;
@@ -228,18 +276,26 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
                 for (int i = 0; i < 4; ++i) {
                     const int rr = i * 4 + rq;
                     const float4 t = *reinterpret_cast<const float4*>(stg + rr * 68 + cc);
-                    const int m = mw0 + mi * 16 + rr;
-                    if (m >= a.M) continue;
                     float v[4] = {t.x, t.y, t.z, t.w};
                     const float4 bias4 = *reinterpret_cast<const float4*>(sbias + cc);
                     epi_apply4(alpha, 0, v, bias4, make_uint2(0, 0), a.res != nullptr, pf.rs[g % NB][mj][i]);
-                    NT_STORE(reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + (size_t)m * a.ldo + n), (f32x4{v[0], v[1], v[2], v[3]}));
+                    epi_store128(__builtin_bit_cast(u32x4, f32x4{v[0], v[1], v[2], v[3]}), ro, oo + epi_row_off(mi * 16 + i * 4, ldo_b));
                 }
             }
         }
     } else {
         const int cc = (lane & 7) * 8, rq = lane >> 3;
-        const int n = nw0 + cc;
+        // `out`: bf16, or gelu'(x) as 8-bit codes (ldo then counts bytes); `out2`: bf16; `out8`: one byte per value
+        const bool out_c8 = ACT == 1 && Q8 != 2 && a.aux8;
+        const unsigned es_o = out_c8 ? 1u : 2u, ldo_b = (unsigned)a.ldo * es_o;
+        const epi_rsrc_t ro = epi_rsrc(a.out, ldo_b, mw0, (unsigned)nw0 * es_o, a.M);
+        const unsigned oo = (unsigned)rq * ldo_b + (unsigned)cc * es_o;
+        const unsigned ldo2_b = ACT == 1 ? (unsigned)a.ldo2 * 2u : 0u;
+        const epi_rsrc_t ro2 = epi_rsrc(ACT == 1 ? a.out2 : nullptr, ldo2_b, mw0, (unsigned)nw0 * 2u, a.M);
+        const unsigned oo2 = (unsigned)rq * ldo2_b + (unsigned)cc * 2u;
+        const unsigned ldo8_b = Q8 != 0 ? (unsigned)a.ldo8 : 0u;
+        const epi_rsrc_t ro8 = epi_rsrc(Q8 != 0 ? a.out8 : nullptr, ldo8_b, mw0, (unsigned)nw0, a.M);
+        const unsigned oo8 = (unsigned)rq * ldo8_b + (unsigned)cc;
         const unsigned raddr = stg_lds + (rq * 68 + cc) * 4, baddr = sbias_lds + cc * 4;      // rows rq and rq + 8: 2176 B apart
         constexpr int AG = EpiPrefetch<MI>::AG, NG = MI / AG;
         float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};       // this lane's 8 columns, summed over the rows it handles
@@ -263,9 +319,9 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
                 epi_lds_wait();
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const int rr = i * 8 + rq;
-                    const int m = mw0 + mi * 16 + rr;
-                    if (m >= a.M) continue;
+                    // (no row mask: the stores of a row at or behind M are dropped by the range check; such a row repeats row M - 1 -
+                    //  the operand rows are clamped - so it changes no amax either, and the column sums leave it out below)
+                    const int row = mi * 16 + i * 8;              // wave-uniform row step from the lane's first row
                     float v0[4] = {tq[i][0][0], tq[i][0][1], tq[i][0][2], tq[i][0][3]}, v1[4] = {tq[i][1][0], tq[i][1][1], tq[i][1][2], tq[i][1][3]};
                     // (no residual here: it exists for fp32 output only - an optional per-row load in this loop would put a
                     //  vmcnt(0) at its join point in front of every row group's stores, taken or not)
@@ -288,8 +344,11 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
                     epi_apply4(alpha, ACT, v1, bias_hi, make_uint2(ax[2], ax[3]), false, r1);
                     }
                     if (colsum) {
+                        // only a row block that straddles M (wave-uniform test) masks its rows
+                        if (mi * 16 + 16 <= a.M - mw0 || row + (lane >> 3) < a.M - mw0) {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { cs[j] += v0[j]; cs[4 + j] += v1[j]; }
+                            for (int j = 0; j < 4; ++j) { cs[j] += v0[j]; cs[4 + j] += v1[j]; }
+                        }
                     }
                     uint4 o;
                     if (ACT == 1) {
@@ -307,9 +366,9 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
                         auto enc = [](float g, unsigned sel, unsigned old) { return __builtin_amdgcn_cvt_pk_u8_f32(fmaf(g, GP8_STEPS, GP8_BIAS * GP8_STEPS), sel, old); };
                         unsigned c0 = enc(gelu_erf_grad(v0[0]), 0, 0); c0 = enc(gelu_erf_grad(v0[1]), 1, c0); c0 = enc(gelu_erf_grad(v0[2]), 2, c0); c0 = enc(gelu_erf_grad(v0[3]), 3, c0);
                         unsigned c1 = enc(gelu_erf_grad(v1[0]), 0, 0); c1 = enc(gelu_erf_grad(v1[1]), 1, c1); c1 = enc(gelu_erf_grad(v1[2]), 2, c1); c1 = enc(gelu_erf_grad(v1[3]), 3, c1);
-                        *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(a.out) + (size_t)m * a.ldo + n) = make_uint2(c0, c1);
+                        epi_store64(u32x2{c0, c1}, ro, oo + epi_row_off(row, ldo_b));
                     } else
-                    if (Q8 != 2 || a.out) NT_STORE(reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(a.out) + (size_t)m * a.ldo + n), (u32x4{o.x, o.y, o.z, o.w}));
+                    if (Q8 != 2 || a.out) epi_store128(u32x4{o.x, o.y, o.z, o.w}, ro, oo + epi_row_off(row, ldo_b));
                     if (Q8 == 2 && ACT != 1 && a.out8) {
                         // fp8 backward: the e5m2 copy of this output gradient, the operand of the next input-gradient GEMM
                         auto c8 = [&](float x) { q8max = fmaxf(q8max, fabsf(x)); return __builtin_amdgcn_fmed3f(x * q8s, -57344.f, 57344.f); };
@@ -317,14 +376,14 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
                         w0 = __builtin_amdgcn_cvt_pk_bf8_f32(c8(v0[2]), c8(v0[3]), w0, true);
                         int w1 = __builtin_amdgcn_cvt_pk_bf8_f32(c8(v1[0]), c8(v1[1]), 0, false);
                         w1 = __builtin_amdgcn_cvt_pk_bf8_f32(c8(v1[2]), c8(v1[3]), w1, true);
-                        *reinterpret_cast<uint2*>(a.out8 + (size_t)m * a.ldo8 + n) = make_uint2((unsigned)w0, (unsigned)w1);
+                        epi_store64(u32x2{(unsigned)w0, (unsigned)w1}, ro8, oo8 + epi_row_off(row, ldo8_b));
                     }
                     if (ACT == 1) {
                         uint4 gq;
                         gq.x = pack_bf2(gelu_erf(v0[0]), gelu_erf(v0[1])); gq.y = pack_bf2(gelu_erf(v0[2]), gelu_erf(v0[3]));
                         gq.z = pack_bf2(gelu_erf(v1[0]), gelu_erf(v1[1])); gq.w = pack_bf2(gelu_erf(v1[2]), gelu_erf(v1[3]));
                         // (fp8 forward: `out2` may be NULL when fc2 and its weight gradient both read the e4m3 copy)
-                        if (Q8 != 1 || a.out2) NT_STORE(reinterpret_cast<u32x4*>(a.out2 + (size_t)m * a.ldo2 + n), (u32x4{gq.x, gq.y, gq.z, gq.w}));
+                        if (Q8 != 1 || a.out2) epi_store128(u32x4{gq.x, gq.y, gq.z, gq.w}, ro2, oo2 + epi_row_off(row, ldo2_b));
                         if (Q8 == 1 && a.out8) {
                             const float q = q8s;
                             auto q8 = [&](float x) { const float gx = gelu_erf(x); q8max = fmaxf(q8max, fabsf(gx)); return __builtin_amdgcn_fmed3f(gx * q, -448.f, 448.f); };
@@ -332,7 +391,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
                             w0 = __builtin_amdgcn_cvt_pk_fp8_f32(q8(v0[2]), q8(v0[3]), w0, true);
                             int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(q8(v1[0]), q8(v1[1]), 0, false);
                             w1 = __builtin_amdgcn_cvt_pk_fp8_f32(q8(v1[2]), q8(v1[3]), w1, true);
-                            *reinterpret_cast<uint2*>(a.out8 + (size_t)m * a.ldo8 + n) = make_uint2((unsigned)w0, (unsigned)w1);
+                            epi_store64(u32x2{(unsigned)w0, (unsigned)w1}, ro8, oo8 + epi_row_off(row, ldo8_b));
                         }
                     }
                 }
@@ -352,7 +411,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4]
             }
             if (rq == 0) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) atomicAdd(colsum + n + j, cs[j]);
+                for (int j = 0; j < 8; ++j) atomicAdd(colsum + nw0 + (lane & 7) * 8 + j, cs[j]);
             }
         }
     }
@@ -471,9 +530,13 @@ __global__ __launch_bounds__(128 * NWN) void gemm_nt_kernel(GemmNtArgs a) {
         nt_epilogue_stage_bias(a, smem + BUF_BYTES, wave, lane, em, en);
         // (the epilogue runs with no LDS-DMA in flight, see gemm_nt8_kernel: the next tile's first slab is requested after it)
         const bool has_next = v + (int)gridDim.x < ntiles;
+        // (an opaque copy of the lane id, as in gemm_nt8_kernel: the epilogue's per-lane byte offsets do not depend on the tile, and
+        //  hoisted out of the tile loop - one register per row step and stream - they are spilled)
+        int elane = lane;
+        asm volatile("" : "+v"(elane));
         EpiPrefetch<MIT> pf;
-        nt_epilogue_prefetch<ACT, MIT>(a, pf, lane, em, en);
-        nt_epilogue<ACT, MIT>(a, acc, pf, smem + BUF_BYTES, wave, lane, em, en);
+        nt_epilogue_prefetch<ACT, MIT>(a, pf, elane, em, en);
+        nt_epilogue<ACT, MIT>(a, acc, pf, smem + BUF_BYTES, wave, elane, em, en);
         if (has_next) {
             set_tile(v + gridDim.x);
             stage(0, 0);
@@ -1242,6 +1305,17 @@ extern "C" int avs_gemm_nt_plan(int M, int N, int K, int* family, int* workgroup
     return 0;
 }
 
+// The nt epilogue addresses each of its streams with 32-bit byte offsets (epi_rsrc): rows x bytes per row must stay below 4 GiB.
+// (The table a res_idx gather reads from has no height here: it must lie within 4 GiB of `res`.)
+static bool nt_streams_fit(int M, const void* p0, long long rb0, const void* p1, long long rb1, const void* p2, long long rb2, const void* p3, long long rb3,
+                           const void* p4, long long rb4) {
+    const void* ps[5] = {p0, p1, p2, p3, p4};
+    const long long rbs[5] = {rb0, rb1, rb2, rb3, rb4};
+    for (int i = 0; i < 5; ++i)
+        if (ps[i] && (rbs[i] <= 0 || (unsigned long long)M * (unsigned long long)rbs[i] >= (1ull << 32))) return false;
+    return true;
+}
+
 static int gemm_nt_launch(const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
                           const float* bias, const float* res, long long ldr, const int* res_idx, const bf16_t* aux,
                           long long ldaux, void* out, long long ldo, int out_f32, bf16_t* out2, long long ldo2,
@@ -1267,6 +1341,23 @@ static int gemm_nt_launch(const bf16_t* A, long long lda, const bf16_t* B, long 
     AVS_CHECK_ARG(!(out_f32 && colsum), "gemm_nt: the fused column sum is implemented for bf16 output");
     AVS_CHECK_ARG(!res || out_f32, "gemm_nt: the residual add is implemented for fp32 output");
     AVS_CHECK_ARG(scale_cols >= 0 && scale_cols <= N && (scale_cols % 64) == 0, "gemm_nt: scale_cols must be a multiple of 64 within N");
+    // the epilogue's 32-bit byte offsets (epi_rsrc): a call whose streams do not fit is two calls over halves of the rows
+    const long long eo = out_f32 ? 4 : (aux8 && act == 1) ? 1 : 2, eaux = (aux8 && act == 2) ? 1 : 2;      // bytes per element of `out` / `aux` (codes: one)
+    auto fits = [&](int rows) { return nt_streams_fit(rows, out, ldo * eo, out2, ldo2 * 2, res_idx ? nullptr : res, ldr * 4, aux, ldaux * eaux, nullptr, 0); };
+    if (!fits(M)) {
+        const int M1 = ((M / 2 + 255) / 256) * 256;                            // (a multiple of 256, like m_split)
+        AVS_CHECK_ARG(M1 < M && fits(M1), "gemm_nt: an epilogue stream of M=%d rows exceeds 4 GiB even in two halves", M);
+        for (int h = 0; h < 2; ++h) {
+            const long long r0 = h ? M1 : 0;
+            const int rc = gemm_nt_launch(A + r0 * lda, lda, B, ldb, h ? M - M1 : M1, N, K, bias, res && !res_idx ? res + r0 * ldr : res, ldr,
+                                          res_idx ? res_idx + r0 : nullptr, aux ? reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(aux) + r0 * ldaux * eaux) : nullptr,
+                                          ldaux, reinterpret_cast<char*>(out) + r0 * ldo * eo, ldo, eo == 1 ? 2 : out_f32, out2 ? out2 + r0 * ldo2 : nullptr, ldo2,
+                                          alpha, eaux == 1 ? 3 : act, scale_cols, col_scale, colsum,
+                                          m_split == 0x7fffffff ? m_split : (m_split > r0 ? (int)(m_split - r0) : 0), B2, bias2, colsum2, stream);
+            if (rc != 0) return rc;
+        }
+        return 0;
+    }
     GemmNtArgs a{A, lda, B, ldb, M, N, K, bias, res, ldr, res_idx, aux, ldaux, out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols, col_scale, colsum, M,
                  m_split, B2, bias2, colsum2, nullptr, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, 0.f, 0, aux8};
     // 256^2 tiles once they give half the CUs a workgroup; otherwise 128^2 (4x the workgroups, two per CU).  Rounds 1 - 4 asked for 224 tiles; between
@@ -1423,6 +1514,7 @@ extern "C" int avs_gemm_nt_fp8(const uint8_t* A, long long lda, const uint8_t* B
                                int a_e5m2, const bf16_t* aux, long long ldaux, float* colsum, float* colsum2, hipStream_t stream) {
     // 8-bit gelu' (fp8 backward): out_f32 == 2 with act 1 - `out` receives the codes (ldo in bytes); a_e5m2 == 2 with act 2 - `aux` holds them (ldaux in bytes)
     const bool gp8 = (out_f32 == 2) || (a_e5m2 == 2);
+    const bool out_gp8 = out_f32 == 2, aux_gp8 = a_e5m2 == 2;
     AVS_CHECK_ARG(out_f32 != 2 || (act == 1 && !a_e5m2 && out && (ldo % 8) == 0 && ldo >= N), "gemm_nt_fp8: out_f32 == 2 (8-bit gelu') goes with act 1 of the forward form");
     AVS_CHECK_ARG(a_e5m2 != 2 || (act == 2 && aux && ldaux >= N), "gemm_nt_fp8: a_e5m2 == 2 (8-bit gelu' operand) goes with act 2");
     if (out_f32 == 2) out_f32 = 0;
@@ -1444,6 +1536,8 @@ extern "C" int avs_gemm_nt_fp8(const uint8_t* A, long long lda, const uint8_t* B
     AVS_CHECK_ARG(!colsum || (!out_f32 && a_e5m2), "gemm_nt_fp8: the fused column sum goes with the bf16 output of the input-gradient form");
     AVS_CHECK_ARG(scale_cols >= 0 && scale_cols <= N && (scale_cols % 64) == 0, "gemm_nt_fp8: scale_cols must be a multiple of 64 within N");
     AVS_CHECK_ARG((qa == nullptr) == (qw == nullptr), "gemm_nt_fp8: qa and qw go together");
+    AVS_CHECK_ARG(nt_streams_fit(M, out, ldo * (out_f32 ? 4 : out_gp8 ? 1 : 2), out2, ldo2 * 2, res, ldr * 4, aux, ldaux * (aux_gp8 ? 1 : 2), out8, ldo8),
+                  "gemm_nt_fp8: every epilogue stream (M=%d rows x its leading dimension) must stay below 4 GiB", M);
     const bool dual = m_split > 0 && m_split < M;
     AVS_CHECK_ARG(!dual || ((m_split % 256) == 0 && B2 && (bias == nullptr) == (bias2 == nullptr) && qa && qw2 && (colsum == nullptr) == (colsum2 == nullptr)),
                   "gemm_nt_fp8: two weight sets need m_split %% 256 == 0, B2, bias2 / colsum2 mirroring bias / colsum, and device records (qa, qw, qw2)");

@@ -1,4 +1,4 @@
-// Diagnostic (tools/valu_rate.py): issue cost of the VALU instructions the attention softmax is made of, in shader-clock cycles per
+// Diagnostic (tools/valu_rate.py): issue cost of the VALU instructions the attention softmax is made of (and of the integer multiplies of address arithmetic), in shader-clock cycles per
 // wave64 instruction and SIMD: 1, 2 or 4 waves per SIMD run a long unrolled stream of independent instructions of one kind; cycles come from
 // s_memtime, so the figure does not depend on the clock the power management picks.
 #include <hip/hip_runtime.h>
@@ -19,6 +19,20 @@ __global__ __launch_bounds__(1024) void valu_rate_kernel(float* out, unsigned lo
             if (KIND == 3) asm volatile("v_cvt_pk_bf16_f32 %0, %0, %0" : "+v"(r[i]));
             if (KIND == 6) asm volatile("v_rcp_f32 %0, %0" : "+v"(r[i]));
             if (KIND == 7) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(r[i]));
+        }
+        if (KIND == 8) {                      // the integer multiplies of 64-bit address arithmetic ((size_t)row * ld + col)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) asm volatile("v_mul_lo_u32 %0, %0, %0" : "+v"(r[i]));
+        }
+        if (KIND == 9) {
+#pragma unroll
+            for (int i = 0; i < 16; i += 2) {
+                typedef float f2 __attribute__((ext_vector_type(2)));
+                f2 v = {r[i], r[i + 1]};
+                asm volatile("v_mad_u64_u32 %0, vcc, %1, %1, %0" : "+v"(v) : "v"(r[i]) : "vcc");      // 2 per pair: 16 instructions per iteration like the others
+                asm volatile("v_mad_u64_u32 %0, vcc, %1, %1, %0" : "+v"(v) : "v"(r[i]) : "vcc");
+                r[i + 1] = v[1];
+            }
         }
         if (KIND == 4 || KIND == 5) {
 #pragma unroll
@@ -50,7 +64,7 @@ extern "C" int valu_rate(int kind, void* out, void* cycles, int blocks, int thre
     float* o = (float*)out;
     unsigned long long* c = (unsigned long long*)cycles;
 #define K(n) case n: hipLaunchKernelGGL(valu_rate_kernel<n>, dim3(blocks), dim3(threads), 0, s, o, c, iters); break;
-    switch (kind) { K(0) K(1) K(2) K(3) K(4) K(5) K(6) K(7) default: return -2; }
+    switch (kind) { K(0) K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8) K(9) default: return -2; }
 #undef K
     return (int)hipGetLastError();
 }

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Issue cost (shader cycles per wave64 instruction per SIMD) of the VALU instructions the attention softmax is made of.
+"""Issue cost (shader cycles per wave64 instruction per SIMD) of the VALU instructions the attention softmax is made of, and of the
+integer multiplies of 64-bit address arithmetic (v_mul_lo_u32, v_mad_u64_u32: what the GEMM epilogues no longer spend per row).
     python tools/valu_rate.py"""
 import ctypes
 import os
@@ -20,7 +21,7 @@ def main():
     out = torch.zeros(blocks * 1024, device="cuda")
     cyc = torch.zeros(blocks, 2, dtype=torch.int64, device="cuda")
     for kind, name in ((1, "v_mul_f32"), (7, "v_fma_f32"), (2, "v_max3_f32"), (3, "v_cvt_pk_bf16_f32"), (4, "v_pk_mul_f32 (2 elements)"),
-                       (5, "v_pk_add_f32 (2 elements)"), (0, "v_exp_f32"), (6, "v_rcp_f32")):
+                       (5, "v_pk_add_f32 (2 elements)"), (0, "v_exp_f32"), (6, "v_rcp_f32"), (8, "v_mul_lo_u32"), (9, "v_mad_u64_u32")):
         res = []
         for wps in (1, 2, 4):
             for _ in range(2):
