@@ -1274,232 +1274,266 @@ extern "C" int avs_gemm_set_nt8(int on) { return avs_tuning_set("gemm_nt8", on ?
 extern "C" int avs_gemm_set_tile_height(int h) { return avs_tuning_set("nt_tile_h", h); }
 extern "C" int avs_gemm_set_tile(int tile) { return avs_tuning_set("gemm_tile", tile); }
 
-// Host-side choice of the kernel family of a forward / input-gradient GEMM (knobs gemm_tile, nt_big_min, gemm_ring, cu_reserve included; no device
-// work).  gemm_nt_launch takes exactly these decisions; avs_gemm_nt_plan exports them so that the dispatch thresholds are pinned by the CPU tests.
-enum { NT_TWOBUF = 0, NT_RING = 1, NT_RING_HALF = 2, NT_TWOBUF_HALF = 3, NT_PERSISTENT = 4 };
-static bool nt_use_big(int M, int N) {
-    const int force = g_force_tile;
-    const int big_tiles = ceil_div(M, 256) * (N / 256);
-    const int big_min = avs_tuning().nt_big_min > 0 ? avs_tuning().nt_big_min : avs_persistent_slots() / 2;
-    return force == 256 ? (N % 256) == 0 : force == 128 ? false : ((N % 256) == 0 && big_tiles >= big_min);
+// Every GEMM kernel instantiation of this file with the dynamic LDS it runs in: the one-time hipFuncSetAttribute pass walks these tables
+// and every launch takes its LDS size from the entry it launches.  nt kernels by (act, NtKernel); an fp8 form the entry point refuses is NULL.
+struct GemmKernel { const void* fn; int lds, block; };      // kernel handle, dynamic LDS bytes, threads per workgroup
+enum NtKernel {                 // the first seven in the order avs_gemm_nt_launch_plan reports them
+    NTK_TWOBUF128 = 0,          // gemm_nt_kernel<., 2, 4>      128 x 128 tiles, two buffers
+    NTK_TWOBUF128_HALF,         //                              ... every row as 64 x 128 half-height tiles (m_full = 0)
+    NTK_RING,                   // gemm_nt_ring_kernel<., 4>    128 x 128 tiles, three K-slabs in flight
+    NTK_RING_HALF,              // gemm_nt_ring_kernel<., 2>    64 x 128 tiles
+    NTK_TWOBUF256,              // gemm_nt_kernel<., 4, 8>      256 x 256 tiles, rows from m_full as 128 x 256
+    NTK_NT8_ONE,                // gemm_nt8_kernel<., 0, 4, 4>  8-phase, every tile 256 rows
+    NTK_NT8_TWO,                // gemm_nt8_kernel<., 0, 4, 3>  8-phase, tiles [0, tb) 256 rows, the others 224
+    NTK_FP8,                    // gemm_nt8_kernel<., 1>        fp8 forward (act 0 | 1)
+    NTK_FP8_DGRAD,              // gemm_nt8_kernel<., 2>        fp8 input gradient (act 0 | 2)
+    NTK_COUNT
+};
+template <int ACT, int FP8>
+static const void* nt8_fp8_kernel() {
+    if constexpr ((FP8 == 1 && ACT == 2) || (FP8 == 2 && ACT == 1)) return nullptr;
+    else return (const void*)gemm_nt8_kernel<ACT, FP8>;
 }
-// the 128 x 128 side: `whole` = every row in full-height tiles (not the remainder rows of a persistent launch)
-static int nt_small_family(int M, int N, int K, bool whole) {
-    const int nwg = ceil_div(M, BM) * (N / BN);
-    if (avs_tuning().gemm_ring == 2 && 2 * nwg <= avs_persistent_slots() && whole) return K >= 256 ? NT_RING_HALF : NT_TWOBUF_HALF;
-    if (avs_tuning().gemm_ring && nwg <= avs_persistent_slots() && K >= 256 && whole) return NT_RING;
-    return NT_TWOBUF;
+template <int ACT>
+static const GemmKernel nt_kernels[NTK_COUNT] = {
+    {(const void*)gemm_nt_kernel<ACT, 2, 4>, 65536, 256},       {(const void*)gemm_nt_kernel<ACT, 2, 4>, 65536, 256},
+    {(const void*)gemm_nt_ring_kernel<ACT>, 131072, 256},       {(const void*)gemm_nt_ring_kernel<ACT, 2>, 98304, 256},
+    {(const void*)gemm_nt_kernel<ACT, 4, 8>, 131072, 512},
+    {(const void*)gemm_nt8_kernel<ACT, 0, 4, 4>, 131072, 512},  {(const void*)gemm_nt8_kernel<ACT, 0, 4, 3>, 131072, 512},
+    {nt8_fp8_kernel<ACT, 1>(), 131072, 512},                    {nt8_fp8_kernel<ACT, 2>(), 131072, 512},
+};
+static const GemmKernel* const nt_kernels_by_act[3] = {nt_kernels<0>, nt_kernels<1>, nt_kernels<2>};      // the one place `act` becomes a template argument
+enum TnKernel { TNK_TWOBUF128 = 0, TNK_TWOBUF256, TNK_TN8, TNK_TN8_FP8, TNK_COUNT };
+struct GemmTn8Args;
+__global__ __launch_bounds__(512) void gemm_tn8f_kernel(GemmTn8Args g);      // (defined with the fp8 weight gradients below)
+static const GemmKernel tn_kernels[TNK_COUNT] = {
+    {(const void*)gemm_tn_kernel<2, 2>, 65536, 256}, {(const void*)gemm_tn_kernel<4, 4>, 131072, 512}, {(const void*)gemm_tn8_kernel<0>, 131072, 512},
+    {(const void*)gemm_tn8f_kernel, 98304, 512},
+};
+
+// first call of any GEMM entry point: every kernel above is allowed its dynamic LDS.  A failure leaves the pass to be tried again.
+static int gemm_kernels_ready(const char* who) {
+    static bool done = false;
+    if (done) return 0;
+    hipError_t e = hipSuccess;
+    const GemmKernel* const tables[4] = {nt_kernels<0>, nt_kernels<1>, nt_kernels<2>, tn_kernels};
+    for (int t = 0; t < 4; ++t)
+        for (int i = 0; i < (t < 3 ? NTK_COUNT : TNK_COUNT) && e == hipSuccess; ++i)
+            if (tables[t][i].fn) e = hipFuncSetAttribute(tables[t][i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, tables[t][i].lds);
+    if (e != hipSuccess) {
+        avs_set_error("%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+        return -1;
+    }
+    done = true;
+    return 0;
+}
+
+// kernel<<<grid, k.block, k.lds, stream>>>(a) for a table entry (the call that statement compiles to; AVS_LAUNCH_CHECK picks up its error)
+template <class Args>
+static void gemm_launch(const GemmKernel& k, int grid, Args& a, hipStream_t stream) {
+    void* argv[1] = {&a};
+    (void)hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), argv, k.lds, stream);
+}
+
+// Host-side plan of ONE dispatch of a forward / input-gradient GEMM: pure arithmetic over the shape, the knobs (gemm_tile, nt_big_min, gemm_ring,
+// gemm_nt8, gemm_persistent, nt_tile_h, nt_grid, cu_reserve) and nothing else - no HIP call, no state.  gemm_nt_launch launches exactly this
+// (kernel, grid, block, LDS) and passes tb / m_full to the kernel; avs_gemm_nt_launch_plan exports every field, in this order, so that the CPU
+// tests pin the dispatch.  avs_gemm_nt_plan is the older, coarser view (family + a nominal workgroup count).
+enum { NT_TWOBUF = 0, NT_RING = 1, NT_RING_HALF = 2, NT_TWOBUF_HALF = 3, NT_PERSISTENT = 4 };
+struct NtPlan {
+    int kernel;                 // NtKernel
+    int grid, block, lds;       // workgroups, threads per workgroup, dynamic LDS bytes
+    int tb;                     // GemmNtArgs.tb     (NTK_NT8_TWO; 0 elsewhere)
+    int m_full;                 // GemmNtArgs.m_full (NTK_TWOBUF256: the rows in 256-row tiles; NTK_TWOBUF128_HALF: 0; M elsewhere)
+    int tiles;                  // output tiles the grid walks (== grid unless the kernel is persistent)
+    int family;                 // NT_TWOBUF ... NT_PERSISTENT
+};
+constexpr int NT_PLAN_FIELDS = sizeof(NtPlan) / sizeof(int);
+
+// min(256-row tiles, CUs a persistent grid may fill (device CUs - the cu_reserve knob)): one 128-KiB-LDS workgroup per CU walks the tiles
+static int nt_persistent_grid(int tiles) {
+    const int ncu = avs_persistent_slots();
+    return tiles < ncu ? tiles : ncu;
+}
+
+static NtPlan nt_plan(int M, int N, int K, int m_split) {
+    const int ncu = avs_persistent_slots();
+    const int nt_n = N / 256, nt_m = ceil_div(M, 256), big_tiles = nt_m * nt_n;
+    auto plan = [&](int kernel, int family, int tiles, int grid, int tb, int m_full) {
+        return NtPlan{kernel, grid, nt_kernels<0>[kernel].block, nt_kernels<0>[kernel].lds, tb, m_full, tiles, family};
+    };
+    // 256^2 tiles once they give half the CUs a workgroup; otherwise 128^2 (4x the workgroups, two per CU).  Rounds 1 - 4 asked for 224 tiles; between
+    // 128 and 224 the 128^2 tiling needs 512 ... 896 workgroups = a second round on 512 slots, and the persistent kernel on a part of the chip
+    // runs at a higher clock (DESIGN.md 5b): 135 tiles, K = 3072: 78.1 -> 63.8 us, K = 768: 25.8 -> 23.5; 192 tiles: 80.9 -> 68.9, 28.4 -> 25.7; under
+    // 128 tiles the 128^2 tiling fits one round and wins (96 tiles: 48.2 against 62.1 us) - tools/bench_nt_midsize.py, profiles/r05/nt_midsize.log
+    const int big_min = avs_tuning().nt_big_min > 0 ? avs_tuning().nt_big_min : ncu / 2;
+    const bool big = g_force_tile == 256 ? (N % 256) == 0 : g_force_tile == 128 ? false : ((N % 256) == 0 && big_tiles >= big_min);
+    if (!big) {
+        const int nwg = ceil_div(M, BM) * (N / BN), nh = ceil_div(M, BM / 2) * (N / BN);
+        // fewer workgroups than half the CUs: every row as HALF-height (64 x 128) tiles of the same kernel - twice the workgroups on CUs
+        // that would idle (a CU fills its LDS at ~60 GB/s: the 32 KiB K-slab of a 128 x 128 tile takes 0.55 us against 0.25 us of MFMA
+        // work, so small GEMMs are bound by how many CUs pull, profiles/r05/small_gemm_ab.log); bitwise the full tiles' results
+        if (avs_tuning().gemm_ring == 2 && 2 * nwg <= ncu) {
+            if (K >= 256) return plan(NTK_RING_HALF, NT_RING_HALF, nh, nh, 0, M);   // ... of the ring kernel (three K-slabs in flight)
+            return plan(NTK_TWOBUF128_HALF, NT_TWOBUF_HALF, nh, nh, 0, 0);          // (m_full = 0: no row in a full-height tile)
+        }
+        // at most one workgroup per CU: the ring kernel keeps three K-slabs in flight instead of one
+        if (avs_tuning().gemm_ring && nwg <= ncu && K >= 256) return plan(NTK_RING, NT_RING, nwg, nwg, 0, M);
+        return plan(NTK_TWOBUF128, NT_TWOBUF, nwg, nwg, 0, M);
+    }
+    if (g_nt8 >= 1 && K >= 128 && g_persistent && g_force_tile == 0) {
+        // 8-phase kernel, one dispatch: a partial last round costs it the same as handing the leftover rows to the half-height-tile
+        // kernel in a second dispatch (measured: 185.7 vs 186.0 ms/step).  What it can do about a badly filled last round: the R rounds
+        // that 256-row tiles need offer R x CUs tile slots; with some of the row tiles 224 rows high (gemm_nt8_kernel's second height
+        // class) the same rows fill MORE of those slots with CHEAPER tiles (a 224-row tile costs ~0.90 of a 256-row one,
+        // profiles/r03/gemm_tile_height_by_shape.log) - e.g. 1122 tiles = 4.4 rounds of N = 768 become 24 + 1254 tiles in 5 full rounds:
+        // 4.6 tile-times per CU instead of 5.  Two weight sets: their row split is a multiple of 256, so the 256-row class must cover
+        // the first set entirely (every 224-row tile then lies in the second).
+        const bool one_set = m_split >= M || m_split <= 0;
+        const int unit = nt_n * 8 / std::gcd(nt_n, 8);      // the first class holds whole row tiles and a multiple of 8 tiles (XCD classes)
+        int tb = -1;                                          // -1: every tile 256 rows (the one-class kernel)
+        if (one_set && g_force_h == 224) tb = 0;              // every tile 224 rows
+        else if (one_set && g_force_h == 240) tb = ((nt_m / 2) * nt_n / unit) * unit;
+        else if (g_force_h == 0) {
+            const int rounds = ceil_div(big_tiles, ncu);
+            const int nrt = (rounds * ncu) / nt_n;            // row tiles the slots of those rounds hold
+            // a row tiles of 256 + b of 224 must cover M: b <= (nrt * 256 - M) / 32
+            int b = (int)(((long long)nrt * 256 - M) / 32);
+            if (b > nrt) b = nrt;
+            if (b > 0) {
+                int ta = ((nrt - b) * nt_n + unit - 1) / unit * unit;       // first-class tiles, rounded UP (fewer small tiles: still covers M)
+                if (!one_set && ta / nt_n * 256 < m_split) ta = ceil_div(ceil_div(m_split, 256) * nt_n, unit) * unit;
+                if (ta / nt_n <= nrt) {
+                    const int na = ta / nt_n, nb = ceil_div(M - (na * 256 < M ? na * 256 : M), 224);
+                    // tile-times of the busiest CU: every workgroup meets its first-class tiles first, then the others
+                    const int nbig = ceil_div(ta, ncu), nall = ceil_div((na + nb) * nt_n, ncu);
+                    const double cost = nbig + 0.90 * (nall - nbig);
+                    if (nb > 0 && nall <= rounds && cost < 0.98 * rounds) tb = ta;
+                }
+            }
+        }
+        const int rest = tb < 0 ? 0 : M - (tb / nt_n) * 256;                  // rows of the 224-row class
+        const int tiles = tb < 0 ? big_tiles : tb + ceil_div(rest > 0 ? rest : 0, 224) * nt_n;
+        // nt_grid: cap the persistent grid (tools/bench_stagger.py: two half-chip GEMMs side by side on two streams)
+        const int grid = nt_persistent_grid(tiles), gcap = avs_tuning().nt_grid;
+        return plan(tb < 0 ? NTK_NT8_ONE : NTK_NT8_TWO, NT_PERSISTENT, tiles, gcap > 0 && gcap < grid ? gcap : grid, tb < 0 ? 0 : tb, M);
+    }
+    // Two-buffer kernel (8-phase kernels switched off, or K < 128): with T tiles on C CUs the last of ceil(T/C) rounds may be nearly
+    // empty (1122 tiles -> 4.4 rounds cost 5).  When the last round would be less than half full, the row panels that fill
+    // floor(T/C) rounds stay 256^2 tiles and the remaining rows become 128 x 256 tiles of the SAME launch.
+    int m_full = M;
+    if (g_persistent && g_force_tile == 0 && big_tiles > ncu) {
+        const int rows_full = ((big_tiles / ncu) * ncu) / nt_n;              // row panels inside whole rounds
+        if (rows_full >= 1 && rows_full < nt_m && (big_tiles % ncu) * 2 <= ncu) m_full = rows_full * 256;
+    }
+    const int tiles = ceil_div(m_full, 256) * nt_n + (m_full < M ? ceil_div(M - m_full, 128) * nt_n : 0);
+    return plan(NTK_TWOBUF256, NT_PERSISTENT, tiles, g_persistent ? nt_persistent_grid(tiles) : tiles, 0, m_full);      // gemm_persistent = 0: one workgroup per tile
+}
+
+extern "C" int avs_gemm_nt_launch_plan(int M, int N, int K, int m_split, int* out, int n_out) {
+    AVS_CHECK_ARG(M > 0 && N > 0 && K > 0 && (N % BN) == 0 && (K % BK) == 0 && out && n_out > 0, "gemm_nt_launch_plan: bad arguments M=%d N=%d K=%d n_out=%d", M, N, K, n_out);
+    const NtPlan p = nt_plan(M, N, K, m_split);
+    const int f[NT_PLAN_FIELDS] = {p.kernel, p.grid, p.block, p.lds, p.tb, p.m_full, p.tiles, p.family};
+    for (int i = 0; i < n_out && i < NT_PLAN_FIELDS; ++i) out[i] = f[i];
+    return 0;
 }
 
 extern "C" int avs_gemm_nt_plan(int M, int N, int K, int* family, int* workgroups) {
     AVS_CHECK_ARG(M > 0 && N > 0 && K > 0 && (N % BN) == 0 && (K % BK) == 0 && family && workgroups, "gemm_nt_plan: bad arguments M=%d N=%d K=%d", M, N, K);
-    if (nt_use_big(M, N)) {
-        const int tiles = ceil_div(M, 256) * (N / 256), slots = avs_persistent_slots();
-        *family = NT_PERSISTENT;
-        *workgroups = tiles < slots ? tiles : slots;          // (with two tile heights the 8-phase kernel may walk a few more, cheaper tiles)
-        return 0;
-    }
-    const int fam = nt_small_family(M, N, K, true);
-    *family = fam;
-    *workgroups = ceil_div(M, (fam == NT_RING_HALF || fam == NT_TWOBUF_HALF) ? BM / 2 : BM) * (N / BN);
+    const NtPlan p = nt_plan(M, N, K, 0);
+    *family = p.family;
+    // NT_PERSISTENT: the 256-row tiling's grid (the launch itself may walk more, cheaper tiles or cap its grid: avs_gemm_nt_launch_plan)
+    *workgroups = p.family == NT_PERSISTENT ? nt_persistent_grid(ceil_div(M, 256) * (N / 256)) : p.grid;
     return 0;
 }
 
 // The nt epilogue addresses each of its streams with 32-bit byte offsets (epi_rsrc): rows x bytes per row must stay below 4 GiB.
 // (The table a res_idx gather reads from has no height here: it must lie within 4 GiB of `res`.)
-static bool nt_streams_fit(int M, const void* p0, long long rb0, const void* p1, long long rb1, const void* p2, long long rb2, const void* p3, long long rb3,
-                           const void* p4, long long rb4) {
-    const void* ps[5] = {p0, p1, p2, p3, p4};
-    const long long rbs[5] = {rb0, rb1, rb2, rb3, rb4};
-    for (int i = 0; i < 5; ++i)
-        if (ps[i] && (rbs[i] <= 0 || (unsigned long long)M * (unsigned long long)rbs[i] >= (1ull << 32))) return false;
+struct NtStream { const void* p; long long row_bytes; };
+static bool nt_streams_fit(int M, std::initializer_list<NtStream> streams) {
+    for (const NtStream& s : streams)
+        if (s.p && (s.row_bytes <= 0 || (unsigned long long)M * (unsigned long long)s.row_bytes >= (1ull << 32))) return false;
     return true;
 }
 
-static int gemm_nt_launch(const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
-                          const float* bias, const float* res, long long ldr, const int* res_idx, const bf16_t* aux,
-                          long long ldaux, void* out, long long ldo, int out_f32, bf16_t* out2, long long ldo2,
-                          float alpha, int act, int scale_cols, float col_scale, float* colsum,
-                          int m_split, const bf16_t* B2, const float* bias2, float* colsum2, hipStream_t stream) {
-    AVS_CHECK_ARG(M > 0 && N > 0 && K > 0 && (N % BN) == 0 && (K % BK) == 0, "gemm_nt: need N%%128==0, K%%64==0 (M=%d N=%d K=%d)", M, N, K);
-    AVS_CHECK_ARG(A && B && out, "gemm_nt: null operand");
-    // gelu'(x) as 8-bit fixed-point codes (GP8_*; round 6: the bf16 GEMMs too - EngineOptions.gelu8): out_f32 == 2 with act 1 - `out` receives one byte per
-    // value (ldo in BYTES); act == 3 = act 2 whose `aux` holds those codes (ldaux in bytes).  Same convention as avs_gemm_nt_fp8's out_f32 == 2 / a_e5m2 == 2.
-    int aux8 = 0;
-    if (out_f32 == 2) {
-        AVS_CHECK_ARG(act == 1 && (ldo % 8) == 0 && ldo >= N, "gemm_nt: out_f32 == 2 (8-bit gelu') goes with act 1");
-        out_f32 = 0; aux8 = 1;
-    }
-    if (act == 3) {
-        AVS_CHECK_ARG(aux && ldaux >= N, "gemm_nt: act 3 (act 2 with 8-bit gelu' codes) needs aux");
-        act = 2; aux8 = 1;
-    }
-    AVS_CHECK_ARG((lda % 8) == 0 && (ldb % 8) == 0 && (ldo % (out_f32 ? 4 : 8)) == 0 && (!out2 || (ldo2 % 8) == 0) && (!aux || (ldaux % 8) == 0),
-                  "gemm_nt: leading dimensions must keep 16-byte alignment");
-    AVS_CHECK_ARG(act >= 0 && act <= 2 && (act != 1 || out2) && (act != 2 || aux), "gemm_nt: bad activation arguments");
-    AVS_CHECK_ARG(!(out_f32 && act != 0), "gemm_nt: fp32 output is supported with act 0 only");
-    AVS_CHECK_ARG(!(out_f32 && colsum), "gemm_nt: the fused column sum is implemented for bf16 output");
-    AVS_CHECK_ARG(!res || out_f32, "gemm_nt: the residual add is implemented for fp32 output");
-    AVS_CHECK_ARG(scale_cols >= 0 && scale_cols <= N && (scale_cols % 64) == 0, "gemm_nt: scale_cols must be a multiple of 64 within N");
-    // the epilogue's 32-bit byte offsets (epi_rsrc): a call whose streams do not fit is two calls over halves of the rows
-    const long long eo = out_f32 ? 4 : (aux8 && act == 1) ? 1 : 2, eaux = (aux8 && act == 2) ? 1 : 2;      // bytes per element of `out` / `aux` (codes: one)
-    auto fits = [&](int rows) { return nt_streams_fit(rows, out, ldo * eo, out2, ldo2 * 2, res_idx ? nullptr : res, ldr * 4, aux, ldaux * eaux, nullptr, 0); };
-    if (!fits(M)) {
-        const int M1 = ((M / 2 + 255) / 256) * 256;                            // (a multiple of 256, like m_split)
-        AVS_CHECK_ARG(M1 < M && fits(M1), "gemm_nt: an epilogue stream of M=%d rows exceeds 4 GiB even in two halves", M);
-        for (int h = 0; h < 2; ++h) {
-            const long long r0 = h ? M1 : 0;
-            const int rc = gemm_nt_launch(A + r0 * lda, lda, B, ldb, h ? M - M1 : M1, N, K, bias, res && !res_idx ? res + r0 * ldr : res, ldr,
-                                          res_idx ? res_idx + r0 : nullptr, aux ? reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(aux) + r0 * ldaux * eaux) : nullptr,
-                                          ldaux, reinterpret_cast<char*>(out) + r0 * ldo * eo, ldo, eo == 1 ? 2 : out_f32, out2 ? out2 + r0 * ldo2 : nullptr, ldo2,
-                                          alpha, eaux == 1 ? 3 : act, scale_cols, col_scale, colsum,
-                                          m_split == 0x7fffffff ? m_split : (m_split > r0 ? (int)(m_split - r0) : 0), B2, bias2, colsum2, stream);
-            if (rc != 0) return rc;
-        }
-        return 0;
-    }
-    GemmNtArgs a{A, lda, B, ldb, M, N, K, bias, res, ldr, res_idx, aux, ldaux, out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols, col_scale, colsum, M,
-                 m_split, B2, bias2, colsum2, nullptr, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, 0.f, 0, aux8};
-    // 256^2 tiles once they give half the CUs a workgroup; otherwise 128^2 (4x the workgroups, two per CU).  Rounds 1 - 4 asked for 224 tiles; between
-    // 128 and 224 the 128^2 tiling needs 512 ... 896 workgroups = a second round on 512 slots, and the persistent kernel on a part of the chip
-    // runs at a higher clock (DESIGN.md 5b): 135 tiles, K = 3072: 78.1 -> 63.8 us, K = 768: 25.8 -> 23.5; 192 tiles: 80.9 -> 68.9, 28.4 -> 25.7; under
-    // 128 tiles the 128^2 tiling fits one round and wins (96 tiles: 48.2 against 62.1 us) - tools/bench_nt_midsize.py, profiles/r05/nt_midsize.log
-    const int big_tiles = ceil_div(M, 256) * (N / 256);
-    const bool big = nt_use_big(M, N);
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipSuccess;
-        const void* big_k[3] = {(const void*)gemm_nt_kernel<0, 4, 8>, (const void*)gemm_nt_kernel<1, 4, 8>, (const void*)gemm_nt_kernel<2, 4, 8>};
-        const void* k8[6] = {(const void*)gemm_nt8_kernel<0>, (const void*)gemm_nt8_kernel<1>, (const void*)gemm_nt8_kernel<2>,
-                             (const void*)gemm_nt8_kernel<0, 0, 4, 3>, (const void*)gemm_nt8_kernel<1, 0, 4, 3>, (const void*)gemm_nt8_kernel<2, 0, 4, 3>};
-        for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipFuncSetAttribute(k8[i], hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        const void* small_k[3] = {(const void*)gemm_nt_kernel<0, 2, 4>, (const void*)gemm_nt_kernel<1, 2, 4>, (const void*)gemm_nt_kernel<2, 2, 4>};
-        const void* ring_k[3] = {(const void*)gemm_nt_ring_kernel<0>, (const void*)gemm_nt_ring_kernel<1>, (const void*)gemm_nt_ring_kernel<2>};
-        const void* ring_h[3] = {(const void*)gemm_nt_ring_kernel<0, 2>, (const void*)gemm_nt_ring_kernel<1, 2>, (const void*)gemm_nt_ring_kernel<2, 2>};
-        for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipFuncSetAttribute(ring_h[i], hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-        for (int i = 0; i < 3 && e == hipSuccess; ++i) {
-            e = hipFuncSetAttribute(big_k[i], hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-            if (e == hipSuccess) e = hipFuncSetAttribute(small_k[i], hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            if (e == hipSuccess) e = hipFuncSetAttribute(ring_k[i], hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        }
-        if (e != hipSuccess) {
-            avs_set_error("gemm_nt: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return -1;
-        }
-        attr_done = true;
-    }
-    auto launch_small = [&](const GemmNtArgs& x) {
-        const int nwg = ceil_div(x.M, BM) * (x.N / BN);
-        const int fam = nt_small_family(x.M, x.N, x.K, x.m_full >= x.M);
-        // fewer workgroups than half the CUs: every row as HALF-height (64 x 128) tiles of the same kernel - twice the workgroups on CUs
-        // that would idle (a CU fills its LDS at ~60 GB/s: the 32 KiB K-slab of a 128 x 128 tile takes 0.55 us against 0.25 us of MFMA
-        // work, so small GEMMs are bound by how many CUs pull, profiles/r05/small_gemm_ab.log); bitwise the full tiles' results
-        if (fam == NT_RING_HALF || fam == NT_TWOBUF_HALF) {
-            const int nh = ceil_div(x.M, BM / 2) * (x.N / BN);
-            if (fam == NT_RING_HALF) {         // ... of the ring kernel (three K-slabs in flight)
-                if (act == 0) gemm_nt_ring_kernel<0, 2><<<nh, 256, 98304, stream>>>(x);
-                else if (act == 1) gemm_nt_ring_kernel<1, 2><<<nh, 256, 98304, stream>>>(x);
-                else gemm_nt_ring_kernel<2, 2><<<nh, 256, 98304, stream>>>(x);
-                return;
-            }
-            GemmNtArgs h = x;
-            h.m_full = 0;
-            if (act == 0) gemm_nt_kernel<0, 2, 4><<<nh, 256, 65536, stream>>>(h);
-            else if (act == 1) gemm_nt_kernel<1, 2, 4><<<nh, 256, 65536, stream>>>(h);
-            else gemm_nt_kernel<2, 2, 4><<<nh, 256, 65536, stream>>>(h);
-            return;
-        }
-        // at most one workgroup per CU: the ring kernel keeps three K-slabs in flight instead of one
-        if (fam == NT_RING) {
-            if (act == 0) gemm_nt_ring_kernel<0><<<nwg, 256, 131072, stream>>>(x);
-            else if (act == 1) gemm_nt_ring_kernel<1><<<nwg, 256, 131072, stream>>>(x);
-            else gemm_nt_ring_kernel<2><<<nwg, 256, 131072, stream>>>(x);
-            return;
-        }
-        if (act == 0) gemm_nt_kernel<0, 2, 4><<<nwg, 256, 65536, stream>>>(x);
-        else if (act == 1) gemm_nt_kernel<1, 2, 4><<<nwg, 256, 65536, stream>>>(x);
-        else gemm_nt_kernel<2, 2, 4><<<nwg, 256, 65536, stream>>>(x);
-    };
-    if (big) {
-        // persistent: one 128-KiB-LDS workgroup per CU walks the tiles (grid = min(tiles, CUs))
-        const int ncu = avs_persistent_slots();      // CUs a persistent grid may fill (device CUs - the cu_reserve knob)
-        // Two-buffer kernel (8-phase kernels switched off): with T tiles on C CUs the last of ceil(T/C) rounds may be nearly
-        // empty (1122 tiles -> 4.4 rounds cost 5).  When the last round would be less than half full, the row panels that fill
-        // floor(T/C) rounds stay 256^2 tiles and the remaining rows become 128 x 256 tiles of the SAME launch.
-        const int nt_n = N / 256, nt_m = ceil_div(M, 256);
-        GemmNtArgs b = a;
-        if (g_persistent && g_force_tile == 0 && big_tiles > ncu) {
-            const int rows_full = ((big_tiles / ncu) * ncu) / nt_n;              // row panels inside whole rounds
-            if (rows_full >= 1 && rows_full < nt_m && (big_tiles % ncu) * 2 <= ncu) b.m_full = rows_full * 256;
-        }
-        if (g_nt8 >= 1 && K >= 128 && g_persistent && g_force_tile == 0) {
-            // 8-phase kernel, one dispatch: a partial last round costs it the same as handing the leftover rows to the half-height-tile
-            // kernel in a second dispatch (measured: 185.7 vs 186.0 ms/step).  What it can do about a badly filled last round: the R rounds
-            // that 256-row tiles need offer R x CUs tile slots; with some of the row tiles 224 rows high (gemm_nt8_kernel's second height
-            // class) the same rows fill MORE of those slots with CHEAPER tiles (a 224-row tile costs ~0.90 of a 256-row one,
-            // profiles/r03/gemm_tile_height_by_shape.log) - e.g. 1122 tiles = 4.4 rounds of N = 768 become 21 + 1257 tiles in 5 full rounds:
-            // 4.6 tile-times per CU instead of 5.  Two weight sets: their row split is a multiple of 256, so the 256-row class must cover
-            // the first set entirely (every 224-row tile then lies in the second).
-            const bool one_set = m_split >= M || m_split <= 0;
-            const int unit = nt_n * 8 / std::gcd(nt_n, 8);      // the first class holds whole row tiles and a multiple of 8 tiles (XCD classes)
-            int tb = -1;                                          // -1: every tile 256 rows (the one-class kernel)
-            if (one_set && g_force_h == 224) tb = 0;              // every tile 224 rows
-            else if (one_set && g_force_h == 240) tb = ((nt_m / 2) * nt_n / unit) * unit;
-            else if (g_force_h == 0) {
-                const int rounds = ceil_div(nt_m * nt_n, ncu);
-                const int nrt = (rounds * ncu) / nt_n;            // row tiles the slots of those rounds hold
-                // a row tiles of 256 + b of 224 must cover M: b <= (nrt * 256 - M) / 32
-                int b = (int)(((long long)nrt * 256 - M) / 32);
-                if (b > nrt) b = nrt;
-                if (b > 0) {
-                    int ta = ((nrt - b) * nt_n + unit - 1) / unit * unit;       // first-class tiles, rounded UP (fewer small tiles: still covers M)
-                    if (!one_set && ta / nt_n * 256 < m_split) ta = ceil_div(ceil_div(m_split, 256) * nt_n, unit) * unit;
-                    if (ta / nt_n <= nrt) {
-                        const int na = ta / nt_n, nb = ceil_div(M - (na * 256 < M ? na * 256 : M), 224);
-                        // tile-times of the busiest CU: every workgroup meets its first-class tiles first, then the others
-                        const int nbig = ceil_div(ta, ncu), nall = ceil_div((na + nb) * nt_n, ncu);
-                        const double cost = nbig + 0.90 * (nall - nbig);
-                        if (nb > 0 && nall <= rounds && cost < 0.98 * rounds) tb = ta;
-                    }
-                }
-            }
-            a.tb = tb < 0 ? 0 : tb;
-            const int tiles8 = tb < 0 ? nt_m * nt_n : tb + ceil_div(M - (tb / nt_n) * 256 > 0 ? M - (tb / nt_n) * 256 : 0, 224) * nt_n;
-            int grid8 = tiles8 < ncu ? tiles8 : ncu;
-            // AVSIAM_NT_GRID: cap the persistent grid (tools/bench_stagger.py: two half-chip GEMMs side by side on two streams)
-            { const int gcap = avs_tuning().nt_grid; if (gcap > 0 && gcap < grid8) grid8 = gcap; }
-#define NT8_LAUNCH(ACT_)                                                                          \
-    do {                                                                                          \
-        if (tb >= 0) gemm_nt8_kernel<ACT_, 0, 4, 3><<<grid8, 512, 131072, stream>>>(a);           \
-        else gemm_nt8_kernel<ACT_, 0, 4, 4><<<grid8, 512, 131072, stream>>>(a);                   \
-    } while (0)
-            if (act == 0) NT8_LAUNCH(0);
-            else if (act == 1) NT8_LAUNCH(1);
-            else NT8_LAUNCH(2);
-#undef NT8_LAUNCH
-            AVS_LAUNCH_CHECK("gemm_nt8");
-            ++g_nt_dispatches;
-            return 0;
-        }
-        const int tiles_b = ceil_div(b.m_full, 256) * nt_n + (b.m_full < M ? ceil_div(M - b.m_full, 128) * nt_n : 0);
-        const int grid = g_persistent ? (tiles_b < ncu ? tiles_b : ncu) : tiles_b;
-        if (act == 0) gemm_nt_kernel<0, 4, 8><<<grid, 512, 131072, stream>>>(b);
-        else if (act == 1) gemm_nt_kernel<1, 4, 8><<<grid, 512, 131072, stream>>>(b);
-        else gemm_nt_kernel<2, 4, 8><<<grid, 512, 131072, stream>>>(b);
-    } else {
-        launch_small(a);
-    }
-    AVS_LAUNCH_CHECK("gemm_nt");
+// the arguments of a bf16 call with one weight set, as the entry points receive them (out_f32 == 2 / act == 3: see gemm_nt_launch)
+static GemmNtArgs nt_args(const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K, const float* bias, const float* res,
+                          long long ldr, const int* res_idx, const bf16_t* aux, long long ldaux, void* out, long long ldo, int out_f32, bf16_t* out2,
+                          long long ldo2, float alpha, int act, int scale_cols, float col_scale, float* colsum) {
+    GemmNtArgs a{};
+    a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.M = M; a.N = N; a.K = K; a.bias = bias; a.res = res; a.ldr = ldr; a.res_idx = res_idx; a.aux = aux; a.ldaux = ldaux;
+    a.out = out; a.ldo = ldo; a.out_f32 = out_f32; a.out2 = out2; a.ldo2 = ldo2; a.alpha = alpha; a.act = act; a.scale_cols = scale_cols; a.col_scale = col_scale;
+    a.colsum = colsum; a.m_full = M; a.m_split = 0x7fffffff; a.out8_scale = 1.0f;      // (no second weight set, no fp8 fields)
+    return a;
+}
+
+// bytes per element of `out` / `aux` (gelu' codes: one)
+static long long nt_out_bytes(const GemmNtArgs& a) { return a.out_f32 ? 4 : (a.aux8 && a.act == 1) ? 1 : 2; }
+static long long nt_aux_bytes(const GemmNtArgs& a) { return (a.aux8 && a.act == 2) ? 1 : 2; }
+
+// rows [r0, r0 + rows) of a call as a call of their own: every stream that has a row per output row starts r0 rows later, and the second
+// weight set starts where it did
+static GemmNtArgs nt_rows(GemmNtArgs a, long long r0, int rows) {
+    a.A += r0 * a.lda;
+    if (a.res_idx) a.res_idx += r0;
+    else if (a.res) a.res += r0 * a.ldr;
+    if (a.aux) a.aux = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(a.aux) + r0 * a.ldaux * nt_aux_bytes(a));
+    a.out = reinterpret_cast<char*>(a.out) + r0 * a.ldo * nt_out_bytes(a);
+    if (a.out2) a.out2 += r0 * a.ldo2;
+    if (a.m_split != 0x7fffffff) a.m_split = a.m_split > r0 ? (int)(a.m_split - r0) : 0;
+    a.M = rows;
+    return a;
+}
+
+// one dispatch: the plan's kernel on the plan's grid, tb / m_full from the plan
+static int nt_dispatch(GemmNtArgs a, hipStream_t stream) {
+    const NtPlan p = nt_plan(a.M, a.N, a.K, a.m_split);
+    a.tb = p.tb;
+    a.m_full = p.m_full;
+    gemm_launch(nt_kernels_by_act[a.act][p.kernel], p.grid, a, stream);
+    AVS_LAUNCH_CHECK(p.kernel == NTK_NT8_ONE || p.kernel == NTK_NT8_TWO ? "gemm_nt8" : "gemm_nt");
     ++g_nt_dispatches;
     return 0;
+}
+
+static int gemm_nt_launch(GemmNtArgs a, hipStream_t stream) {
+    AVS_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0 && (a.N % BN) == 0 && (a.K % BK) == 0, "gemm_nt: need N%%128==0, K%%64==0 (M=%d N=%d K=%d)", a.M, a.N, a.K);
+    AVS_CHECK_ARG(a.A && a.B && a.out, "gemm_nt: null operand");
+    // gelu'(x) as 8-bit fixed-point codes (GP8_*; round 6: the bf16 GEMMs too - EngineOptions.gelu8): out_f32 == 2 with act 1 - `out` receives one byte per
+    // value (ldo in BYTES); act == 3 = act 2 whose `aux` holds those codes (ldaux in bytes).  Same convention as avs_gemm_nt_fp8's out_f32 == 2 / a_e5m2 == 2.
+    if (a.out_f32 == 2) {
+        AVS_CHECK_ARG(a.act == 1 && (a.ldo % 8) == 0 && a.ldo >= a.N, "gemm_nt: out_f32 == 2 (8-bit gelu') goes with act 1");
+        a.out_f32 = 0; a.aux8 = 1;
+    }
+    if (a.act == 3) {
+        AVS_CHECK_ARG(a.aux && a.ldaux >= a.N, "gemm_nt: act 3 (act 2 with 8-bit gelu' codes) needs aux");
+        a.act = 2; a.aux8 = 1;
+    }
+    AVS_CHECK_ARG((a.lda % 8) == 0 && (a.ldb % 8) == 0 && (a.ldo % (a.out_f32 ? 4 : 8)) == 0 && (!a.out2 || (a.ldo2 % 8) == 0) && (!a.aux || (a.ldaux % 8) == 0),
+                  "gemm_nt: leading dimensions must keep 16-byte alignment");
+    AVS_CHECK_ARG(a.act >= 0 && a.act <= 2 && (a.act != 1 || a.out2) && (a.act != 2 || a.aux), "gemm_nt: bad activation arguments");
+    AVS_CHECK_ARG(!(a.out_f32 && a.act != 0), "gemm_nt: fp32 output is supported with act 0 only");
+    AVS_CHECK_ARG(!(a.out_f32 && a.colsum), "gemm_nt: the fused column sum is implemented for bf16 output");
+    AVS_CHECK_ARG(!a.res || a.out_f32, "gemm_nt: the residual add is implemented for fp32 output");
+    AVS_CHECK_ARG(a.scale_cols >= 0 && a.scale_cols <= a.N && (a.scale_cols % 64) == 0, "gemm_nt: scale_cols must be a multiple of 64 within N");
+    // the epilogue's 32-bit byte offsets (epi_rsrc): a call whose streams do not fit is two dispatches over halves of the rows
+    auto fits = [&](int rows) {
+        return nt_streams_fit(rows, {{a.out, a.ldo * nt_out_bytes(a)}, {a.out2, a.ldo2 * 2}, {a.res_idx ? nullptr : a.res, a.ldr * 4}, {a.aux, a.ldaux * nt_aux_bytes(a)}});
+    };
+    const int M1 = fits(a.M) ? a.M : ((a.M / 2 + 255) / 256) * 256;            // (a multiple of 256, like m_split)
+    AVS_CHECK_ARG(M1 == a.M || (M1 < a.M && fits(M1)), "gemm_nt: an epilogue stream of M=%d rows exceeds 4 GiB even in two halves", a.M);
+    if (gemm_kernels_ready("gemm_nt") != 0) return -1;
+    if (M1 == a.M) return nt_dispatch(a, stream);
+    if (const int rc = nt_dispatch(nt_rows(a, 0, M1), stream)) return rc;
+    return nt_dispatch(nt_rows(a, M1, a.M - M1), stream);
 }
 
 extern "C" int avs_gemm_nt_bf16(const bf16_t* A, long long lda, const bf16_t* B, long long ldb, int M, int N, int K,
                                 const float* bias, const float* res, long long ldr, const int* res_idx, const bf16_t* aux,
                                 long long ldaux, void* out, long long ldo, int out_f32, bf16_t* out2, long long ldo2,
                                 float alpha, int act, int scale_cols, float col_scale, float* colsum, hipStream_t stream) {
-    return gemm_nt_launch(A, lda, B, ldb, M, N, K, bias, res, ldr, res_idx, aux, ldaux, out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols,
-                          col_scale, colsum, 0x7fffffff, nullptr, nullptr, nullptr, stream);
+    return gemm_nt_launch(nt_args(A, lda, B, ldb, M, N, K, bias, res, ldr, res_idx, aux, ldaux, out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols,
+                                  col_scale, colsum), stream);
 }
 
 // fp8 (OCP e4m3) operands, fp32 accumulation, the epilogues of the bf16 GEMM for act 0 (alpha, bias, fp32 residual, column-range scale,
@@ -1513,7 +1547,6 @@ extern "C" int avs_gemm_nt_fp8(const uint8_t* A, long long lda, const uint8_t* B
                                const float* qa, const float* qw, float* q8, int m_split, const uint8_t* B2, const float* bias2, const float* qw2,
                                int a_e5m2, const bf16_t* aux, long long ldaux, float* colsum, float* colsum2, hipStream_t stream) {
     // 8-bit gelu' (fp8 backward): out_f32 == 2 with act 1 - `out` receives the codes (ldo in bytes); a_e5m2 == 2 with act 2 - `aux` holds them (ldaux in bytes)
-    const bool gp8 = (out_f32 == 2) || (a_e5m2 == 2);
     const bool out_gp8 = out_f32 == 2, aux_gp8 = a_e5m2 == 2;
     AVS_CHECK_ARG(out_f32 != 2 || (act == 1 && !a_e5m2 && out && (ldo % 8) == 0 && ldo >= N), "gemm_nt_fp8: out_f32 == 2 (8-bit gelu') goes with act 1 of the forward form");
     AVS_CHECK_ARG(a_e5m2 != 2 || (act == 2 && aux && ldaux >= N), "gemm_nt_fp8: a_e5m2 == 2 (8-bit gelu' operand) goes with act 2");
@@ -1536,37 +1569,20 @@ extern "C" int avs_gemm_nt_fp8(const uint8_t* A, long long lda, const uint8_t* B
     AVS_CHECK_ARG(!colsum || (!out_f32 && a_e5m2), "gemm_nt_fp8: the fused column sum goes with the bf16 output of the input-gradient form");
     AVS_CHECK_ARG(scale_cols >= 0 && scale_cols <= N && (scale_cols % 64) == 0, "gemm_nt_fp8: scale_cols must be a multiple of 64 within N");
     AVS_CHECK_ARG((qa == nullptr) == (qw == nullptr), "gemm_nt_fp8: qa and qw go together");
-    AVS_CHECK_ARG(nt_streams_fit(M, out, ldo * (out_f32 ? 4 : out_gp8 ? 1 : 2), out2, ldo2 * 2, res, ldr * 4, aux, ldaux * (aux_gp8 ? 1 : 2), out8, ldo8),
+    AVS_CHECK_ARG(nt_streams_fit(M, {{out, ldo * (out_f32 ? 4 : out_gp8 ? 1 : 2)}, {out2, ldo2 * 2}, {res, ldr * 4}, {aux, ldaux * (aux_gp8 ? 1 : 2)}, {out8, ldo8}}),
                   "gemm_nt_fp8: every epilogue stream (M=%d rows x its leading dimension) must stay below 4 GiB", M);
     const bool dual = m_split > 0 && m_split < M;
     AVS_CHECK_ARG(!dual || ((m_split % 256) == 0 && B2 && (bias == nullptr) == (bias2 == nullptr) && qa && qw2 && (colsum == nullptr) == (colsum2 == nullptr)),
                   "gemm_nt_fp8: two weight sets need m_split %% 256 == 0, B2, bias2 / colsum2 mirroring bias / colsum, and device records (qa, qw, qw2)");
-    static bool attr_done = false;
-    if (!attr_done) {
-        const void* ks[4] = {(const void*)gemm_nt8_kernel<0, 1>, (const void*)gemm_nt8_kernel<1, 1>, (const void*)gemm_nt8_kernel<0, 2>, (const void*)gemm_nt8_kernel<2, 2>};
-        for (int i = 0; i < 4; ++i)
-            if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess) {
-                avs_set_error("gemm_nt_fp8: hipFuncSetAttribute failed");
-                return -1;
-            }
-        attr_done = true;
-    }
+    if (gemm_kernels_ready("gemm_nt_fp8") != 0) return -1;
     // the fp8 matrices as the bf16 matrices they alias (see gemm_nt8_kernel): half the columns, half the leading dimension
-    GemmNtArgs a{reinterpret_cast<const bf16_t*>(A), lda / 2, reinterpret_cast<const bf16_t*>(B), ldb / 2, M, N, K / 2, bias, res, ldr, nullptr, aux, ldaux,
-                 out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols, col_scale, colsum, M, dual ? m_split : 0x7fffffff,
-                 dual ? reinterpret_cast<const bf16_t*>(B2) : nullptr, dual ? bias2 : nullptr, dual ? colsum2 : nullptr,
-                 out8, ldo8, out8_scale, qa, qw, dual ? qw2 : qw, q8, 0.f};
-    a.aux8 = gp8 ? 1 : 0;
-    const int ncu = avs_persistent_slots();      // CUs a persistent grid may fill (device CUs - the cu_reserve knob)
-    const int tiles = ceil_div(M, 256) * (N / 256);
-    const int grid = tiles < ncu ? tiles : ncu;
-    if (a_e5m2) {
-        if (act == 0) gemm_nt8_kernel<0, 2><<<grid, 512, 131072, stream>>>(a);
-        else gemm_nt8_kernel<2, 2><<<grid, 512, 131072, stream>>>(a);
-    } else {
-        if (act == 0) gemm_nt8_kernel<0, 1><<<grid, 512, 131072, stream>>>(a);
-        else gemm_nt8_kernel<1, 1><<<grid, 512, 131072, stream>>>(a);
-    }
+    GemmNtArgs a = nt_args(reinterpret_cast<const bf16_t*>(A), lda / 2, reinterpret_cast<const bf16_t*>(B), ldb / 2, M, N, K / 2, bias, res, ldr, nullptr, aux, ldaux,
+                           out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols, col_scale, colsum);
+    if (dual) { a.m_split = m_split; a.B2 = reinterpret_cast<const bf16_t*>(B2); a.bias2 = bias2; a.colsum2 = colsum2; }
+    a.out8 = out8; a.ldo8 = ldo8; a.out8_scale = out8_scale;
+    a.qa = qa; a.qw = qw; a.qw2 = dual ? qw2 : qw; a.q8 = q8;
+    a.aux8 = (out_gp8 || aux_gp8) ? 1 : 0;
+    gemm_launch(nt_kernels_by_act[act][a_e5m2 ? NTK_FP8_DGRAD : NTK_FP8], nt_persistent_grid(ceil_div(M, 256) * (N / 256)), a, stream);
     AVS_LAUNCH_CHECK("gemm_nt_fp8");
     return 0;
 }
@@ -1579,8 +1595,9 @@ extern "C" int avs_gemm_nt_bf16_dual(const bf16_t* A, long long lda, const bf16_
     AVS_CHECK_ARG(m_split > 0 && m_split < M && (m_split % 256) == 0, "gemm_nt_dual: m_split=%d must be a multiple of 256 inside (0, M=%d)", m_split, M);
     AVS_CHECK_ARG(B2 && (bias == nullptr) == (bias2 == nullptr) && (colsum == nullptr) == (colsum2 == nullptr),
                   "gemm_nt_dual: the second weight set must mirror the first (B2, bias2, colsum2)");
-    return gemm_nt_launch(A, lda, B, ldb, M, N, K, bias, res, ldr, res_idx, aux, ldaux, out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols,
-                          col_scale, colsum, m_split, B2, bias2, colsum2, stream);
+    GemmNtArgs a = nt_args(A, lda, B, ldb, M, N, K, bias, res, ldr, res_idx, aux, ldaux, out, ldo, out_f32, out2, ldo2, alpha, act, scale_cols, col_scale, colsum);
+    a.m_split = m_split; a.B2 = B2; a.bias2 = bias2; a.colsum2 = colsum2;
+    return gemm_nt_launch(a, stream);
 }
 
 // Splits of the token dimension of a weight-gradient launch.  Every split divides the contraction but adds one full-tile fp32 atomic epilogue per
@@ -1627,6 +1644,16 @@ static TnPlan tn_plan(int M, int N1, int N2, int splits) {
     return TnPlan{T, tiles, splits, per};
 }
 
+// ... and of a group launch (avs_gemm_tn_bf16_group3 / avs_gemm_tn_fp8_group3: `tiles` 256^2 tiles of up to three problems): at most one resident
+// round (see tn_splits) and at least two stages per split; t_stage: us per 64-row stage of a tile (bf16 1.3, fp8 1.0)
+static TnPlan tn_group_plan(int M, int tiles, double t_stage) {
+    const int nstages = ceil_div(M, BK);
+    int splits = tn_splits(tiles, nstages, avs_persistent_slots(), t_stage, 0.2);
+    if (splits > nstages / 2) splits = nstages / 2 > 0 ? nstages / 2 : 1;
+    const int per = ceil_div(nstages, splits);
+    return TnPlan{256, tiles, ceil_div(nstages, per), per};
+}
+
 extern "C" int avs_gemm_tn_plan(int M, int N1, int N2, int* tile, int* splits) {
     AVS_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0 && (N1 % 128) == 0 && (N2 % 128) == 0 && tile && splits, "gemm_tn_plan: bad arguments M=%d N1=%d N2=%d", M, N1, N2);
     const TnPlan pl = tn_plan(M, N1, N2, 0);
@@ -1639,30 +1666,18 @@ extern "C" int avs_gemm_tn_bf16(const bf16_t* A, long long lda, const bf16_t* B,
                                 int M, int N1, int N2, int splits, hipStream_t stream) {
     AVS_CHECK_ARG(M > 0 && (N1 % 128) == 0 && (N2 % 128) == 0, "gemm_tn: need N1%%128==0 and N2%%128==0 (N1=%d N2=%d)", N1, N2);
     AVS_CHECK_ARG(A && B && C && (lda % 8) == 0 && (ldb % 8) == 0, "gemm_tn: bad operands");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn8_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        if (e != hipSuccess) {
-            avs_set_error("gemm_tn: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return -1;
-        }
-        attr_done = true;
-    }
-    TnPlan pl = tn_plan(M, N1, N2, splits);
+    if (gemm_kernels_ready("gemm_tn") != 0) return -1;
+    const TnPlan pl = tn_plan(M, N1, N2, splits);
     const bool big = pl.tile == 256;
-    const int tiles = pl.tiles, per = pl.stages_per_split;
-    splits = pl.splits;
-    GemmTnArgs a{A, lda, B, ldb, C, ldc, M, N1, N2, per};
+    const int grid = pl.tiles * pl.splits;
+    GemmTnArgs a{A, lda, B, ldb, C, ldc, M, N1, N2, pl.stages_per_split};
     if (big && g_nt8 >= 1) {
         GemmTnGroupArgs g{};
         g.p[0] = TnProb{A, lda, B, ldb, C, ldc, N1, N2, 0};
-        g.nprob = 1; g.tiles = tiles; g.M = M; g.stages_per_split = per;
-        gemm_tn8_kernel<0><<<tiles * splits, 512, 131072, stream>>>(g);
+        g.nprob = 1; g.tiles = pl.tiles; g.M = M; g.stages_per_split = pl.stages_per_split;
+        gemm_launch(tn_kernels[TNK_TN8], grid, g, stream);
     }
-    else if (big) gemm_tn_kernel<4, 4><<<tiles * splits, 512, 131072, stream>>>(a);
-    else gemm_tn_kernel<2, 2><<<tiles * splits, 256, 65536, stream>>>(a);
+    else gemm_launch(tn_kernels[big ? TNK_TWOBUF256 : TNK_TWOBUF128], grid, a, stream);
     AVS_LAUNCH_CHECK("gemm_tn");
     return 0;
 }
@@ -1845,22 +1860,10 @@ extern "C" int avs_gemm_tn_fp8_group3(const uint8_t* A0, long long lda0, const u
         tiles += (n1s[i] / 256) * (n2s[i] / 256);
         ++n;
     }
-    const int nstages = ceil_div(M, 64);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)gemm_tn8f_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 98304) != hipSuccess) {
-            avs_set_error("gemm_tn_fp8_group3: hipFuncSetAttribute failed");
-            return -1;
-        }
-        attr_done = true;
-    }
-    const int ncu = avs_persistent_slots();      // CUs a persistent grid may fill (device CUs - the cu_reserve knob)
-    int splits = tn_splits(tiles, nstages, ncu, 1.0, 0.2);      // at most one resident round (see tn_splits)
-    if (splits > nstages / 2) splits = nstages / 2 > 0 ? nstages / 2 : 1;
-    const int per = ceil_div(nstages, splits);
-    splits = ceil_div(nstages, per);
-    g.nprob = n; g.tiles = tiles; g.M = M; g.stages_per_split = per;
-    gemm_tn8f_kernel<<<tiles * splits, 512, 98304, stream>>>(g);
+    if (gemm_kernels_ready("gemm_tn_fp8_group3") != 0) return -1;
+    const TnPlan pl = tn_group_plan(M, tiles, 1.0);
+    g.nprob = n; g.tiles = tiles; g.M = M; g.stages_per_split = pl.stages_per_split;
+    gemm_launch(tn_kernels[TNK_TN8_FP8], tiles * pl.splits, g, stream);
     AVS_LAUNCH_CHECK("gemm_tn_fp8_group3");
     return 0;
 }
@@ -1886,28 +1889,16 @@ extern "C" int avs_gemm_tn_bf16_group3(const bf16_t* A0, long long lda0, const b
         tiles += (n1s[i] / 256) * (n2s[i] / 256);
         ++n;
     }
-    const int nstages = ceil_div(M, BK);
-    if (!ok || g_nt8 < 1 || g_force_tile == 128 || n < 2 || nstages < 8) {
+    if (!ok || g_nt8 < 1 || g_force_tile == 128 || n < 2 || ceil_div(M, BK) < 8) {
         for (int i = 0; i < 3; ++i)
             if (As[i])
                 if (int e = avs_gemm_tn_bf16(As[i], las[i], Bs[i], lbs[i], Cs[i], n2s[i], M, n1s[i], n2s[i], 0, stream)) return e;
         return 0;
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)gemm_tn8_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess) {
-            avs_set_error("gemm_tn_group3: hipFuncSetAttribute failed");
-            return -1;
-        }
-        attr_done = true;
-    }
-    const int ncu = avs_persistent_slots();      // CUs a persistent grid may fill (device CUs - the cu_reserve knob)
-    int splits = tn_splits(tiles, nstages, ncu, 1.3, 0.2);      // at most one resident round (see tn_splits)
-    if (splits > nstages / 2) splits = nstages / 2 > 0 ? nstages / 2 : 1;
-    const int per = ceil_div(nstages, splits);
-    splits = ceil_div(nstages, per);
-    g.nprob = n; g.tiles = tiles; g.M = M; g.stages_per_split = per;
-    gemm_tn8_kernel<0><<<tiles * splits, 512, 131072, stream>>>(g);
+    if (gemm_kernels_ready("gemm_tn_group3") != 0) return -1;
+    const TnPlan pl = tn_group_plan(M, tiles, 1.3);
+    g.nprob = n; g.tiles = tiles; g.M = M; g.stages_per_split = pl.stages_per_split;
+    gemm_launch(tn_kernels[TNK_TN8], tiles * pl.splits, g, stream);
     AVS_LAUNCH_CHECK("gemm_tn_group3");
     return 0;
 }

@@ -176,10 +176,24 @@ int avs_gemm_tn_bf16(const avs_bf16* A, long long lda, const avs_bf16* B, long l
 /* The plan avs_gemm_tn_bf16 takes for (M, N1, N2) with splits <= 0 under the current knobs: output tile size (128 | 256) and the number of
  * splits of the token rows.  Host arithmetic only (no device work, callable without a GPU): pins the split heuristic in the CPU test suite. */
 int avs_gemm_tn_plan(int M, int N1, int N2, int* tile, int* splits);
-/* The kernel family avs_gemm_nt_bf16 dispatches (M, N, K) to under the current knobs, and the workgroups it launches: family 0 two-buffer
- * 128 x 128 tiles | 1 LDS-DMA ring, 128 x 128 | 2 ring, 64 x 128 half-height tiles | 3 two-buffer, 64 x 128 | 4 persistent 256 x 256 (8-phase).
- * Host arithmetic only (callable without a GPU). */
+/* The kernel family avs_gemm_nt_bf16 dispatches (M, N, K) to under the current knobs: family 0 two-buffer 128 x 128 tiles | 1 LDS-DMA ring,
+ * 128 x 128 | 2 ring, 64 x 128 half-height tiles | 3 two-buffer, 64 x 128 | 4 the 256 x 256 kernels (8-phase or two-buffer).  workgroups: for
+ * families 0 - 3 the grid launched; for family 4 the NOMINAL min(256-row tiles, avs_persistent_cu_slots()) - the launch itself may walk more,
+ * cheaper 224-row tiles, cap its grid (nt_grid) or start one workgroup per tile (gemm_persistent = 0): avs_gemm_nt_launch_plan gives the real
+ * grid.  A coarse view of that plan, kept for the dispatch thresholds it pins.  Host arithmetic only (callable without a GPU). */
 int avs_gemm_nt_plan(int M, int N, int K, int* family, int* workgroups);
+/* The launch avs_gemm_nt_bf16 (m_split <= 0 or >= M: one weight set) / avs_gemm_nt_bf16_dual (rows from m_split use the second set) makes
+ * for (M, N, K) under the current knobs - the plan the launcher itself consumes, for one dispatch (a call whose epilogue streams exceed
+ * 4 GiB is two dispatches over halves of its rows, each planned like this).  Writes the first min(n_out, 8) of, in this order:
+ *   out[0] kernel   0 two-buffer 128 x 128 | 1 two-buffer, 64 x 128 half-height tiles | 2 ring 128 x 128 | 3 ring, 64 x 128 | 4 two-buffer
+ *                   256 x 256 | 5 8-phase, one tile height (256 rows) | 6 8-phase, two tile heights (256 and 224 rows)
+ *   out[1] grid     workgroups launched          out[2] block   threads per workgroup          out[3] lds   dynamic LDS bytes
+ *   out[4] tb       kernel 6: tiles [0, tb) are 256 rows high, the others 224 (0: every tile 224 rows); 0 for the other kernels
+ *   out[5] m_full   kernel 4: rows [0, m_full) in 256-row tiles, the rest in 128-row tiles; kernel 1: 0; M for the other kernels
+ *   out[6] tiles    output tiles the grid walks (more than grid when the workgroups are persistent)
+ *   out[7] family   as avs_gemm_nt_plan
+ * Host arithmetic only (callable without a GPU). */
+int avs_gemm_nt_launch_plan(int M, int N, int K, int m_split, int* out, int n_out);
 /* up to three weight gradients over the SAME M token rows in one launch: Ci[N1_i, N2_i] (contiguous) += Ai^T . Bi; problem i is absent
  * when Ai is NULL (problem 0 must exist).  A block's fc2 / fc1 / proj gradients (timm Mlp + Attention.proj, cav_mae_base.py:77,138-143)
  * exist at the same time; together they fill the chip with 3 splits of the token rows instead of 7 + 7 + 14, i.e. with 40 % of the fp32

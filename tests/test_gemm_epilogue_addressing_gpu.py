@@ -10,6 +10,8 @@ family runs every epilogue form; references are fp32 products of the same bf16 i
 
 K = 128 everywhere but in the ring family: gemm_nt_ring_kernel is chosen from K = 256 on.
 """
+import ctypes
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -24,15 +26,16 @@ FRONT, BEHIND = 5, 256                      # sentinel rows in front of row 0 an
 SENTINEL = 0xA5
 SPLIT = 256                                 # the dual form's m_split
 
-# knobs that force each kernel family (csrc/gemm.hip nt_use_big / nt_small_family), and its K
+# knobs that force each kernel family (csrc/gemm.hip nt_plan), its K, and the instantiation avs_gemm_nt_launch_plan must name for every case
+K_TWOBUF128, K_TWOBUF128_HALF, K_RING, K_RING_HALF, K_TWOBUF256, K_NT8_ONE, K_NT8_TWO = range(7)
 FAMILIES = {
-    "nt8_two_heights": (dict(nt_big_min=1, nt_tile_h=0), 128),      # gemm_nt8_kernel<., 0, 4, 3>: at these row counts every tile is 224 rows high
-    "nt8_256": (dict(nt_big_min=1, nt_tile_h=256), 128),            # gemm_nt8_kernel<., 0, 4, 4>
-    "tile256": (dict(gemm_tile=256), 128),                          # gemm_nt_kernel<., 4, 8>
-    "tile128": (dict(gemm_tile=128, gemm_ring=0), 128),             # gemm_nt_kernel<., 2, 4>
-    "tile128_half": (dict(gemm_tile=128, gemm_ring=2), 128),        # ... its half-height tiles
-    "ring": (dict(gemm_tile=128, gemm_ring=1), 256),                # gemm_nt_ring_kernel<., 4>
-    "ring_half": (dict(gemm_tile=128, gemm_ring=2), 256),           # gemm_nt_ring_kernel<., 2>
+    "nt8_two_heights": (dict(nt_big_min=1, nt_tile_h=0), 128, K_NT8_TWO),      # gemm_nt8_kernel<., 0, 4, 3>: at these row counts every tile is 224 rows high
+    "nt8_256": (dict(nt_big_min=1, nt_tile_h=256), 128, K_NT8_ONE),            # gemm_nt8_kernel<., 0, 4, 4>
+    "tile256": (dict(gemm_tile=256), 128, K_TWOBUF256),                        # gemm_nt_kernel<., 4, 8>
+    "tile128": (dict(gemm_tile=128, gemm_ring=0), 128, K_TWOBUF128),           # gemm_nt_kernel<., 2, 4>
+    "tile128_half": (dict(gemm_tile=128, gemm_ring=2), 128, K_TWOBUF128_HALF),  # ... its half-height tiles
+    "ring": (dict(gemm_tile=128, gemm_ring=1), 256, K_RING),                   # gemm_nt_ring_kernel<., 4>
+    "ring_half": (dict(gemm_tile=128, gemm_ring=2), 256, K_RING_HALF),         # gemm_nt_ring_kernel<., 2>
 }
 FORMS = ("bf16", "f32", "f32_res", "f32_gather", "scale_cols", "gelu", "gelu_codes", "gelu_bwd", "gelu_bwd_codes", "colsum", "dual")
 
@@ -253,8 +256,12 @@ def test_rows_are_split_when_a_stream_exceeds_4_gib():
 def test_epilogue_addressing(family):
     from avsiam_amd import _lib
     _lib.load()
-    knobs, K = FAMILIES[family]
+    knobs, K, kernel = FAMILIES[family]
+    plan = (ctypes.c_int * 8)()
     with forced(knobs):
         for form, M, N in cases():
+            assert _lib.load().avs_gemm_nt_launch_plan(M, N, K, SPLIT if form == "dual" else 0, plan, 8) == 0
+            # (two weight sets: the 256-row class must cover the first - at these row counts that leaves no 224-row tile, so the one-class kernel runs)
+            assert plan[0] == (K_NT8_ONE if (family, form) == ("nt8_two_heights", "dual") else kernel), (family, form, M, N, list(plan))
             got = run_form(form, M, N, K)
             check_form(form, M, N, K, got)

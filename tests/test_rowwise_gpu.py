@@ -67,6 +67,17 @@ def nt_plan(M, N, K):
     return fam.value, wgs.value
 
 
+K_TWOBUF128, K_TWOBUF128_HALF, K_RING, K_RING_HALF, K_TWOBUF256, K_NT8_ONE, K_NT8_TWO = range(7)     # avs_gemm_nt_launch_plan's kernels
+
+
+def nt_launch_plan(M, N, K, m_split=0):
+    """the launch gemm_nt_launch makes: kernel instantiation, grid, tile-height split (include/avsiam_hip.h)"""
+    from avsiam_amd import _lib
+    out = (ctypes.c_int * 8)()
+    assert _lib.load().avs_gemm_nt_launch_plan(M, N, K, m_split, out, 8) == 0
+    return dict(zip(("kernel", "grid", "block", "lds", "tb", "m_full", "tiles", "family"), out))
+
+
 def tn_plan(M, N1, N2):
     from avsiam_amd import _lib
     tile, splits = ctypes.c_int(0), ctypes.c_int(0)
@@ -207,35 +218,44 @@ NT_BIG_M = (1, 65, 223, 224, 225, 255, 256, 257, 300, 600)
 def test_gemm_nt_persistent_8phase_at_small_shapes(tile_h, grid):
     """The persistent 8-phase 256 x 256 kernel - reached by the suite's other tests only from 9000 rows up - at a few hundred rows
     (nt_big_min = 1): both tile-height classes, two K-tiles (K = 128) and an odd count (K = 320), and with nt_grid = 2 two workgroups that
-    walk the (up to six) tiles."""
+    walk the (up to six) tiles.  At these row counts the automatic heights (0) make every tile 224 rows, as nt_tile_h = 224 does: the
+    two-class instantiation with an empty first class; 256 is the one-class instantiation."""
     chk = Chk("gemm_nt.persistent8")
     with knobs(nt_big_min=1, nt_tile_h=tile_h, nt_grid=grid):
         for K in (128, 320):
             for M in NT_BIG_M:
                 assert nt_plan(M, 512, K)[0] == PERSISTENT
+                p = nt_launch_plan(M, 512, K)
+                assert (p["kernel"], p["tb"]) == ((K_NT8_ONE, 0) if tile_h == 256 else (K_NT8_TWO, 0)), (tile_h, M, K, p)
+                tiles = 2 * -(-M // (256 if tile_h == 256 else 224))
+                assert p["tiles"] == tiles and p["grid"] == (min(grid, tiles) if grid else tiles), (tile_h, grid, M, K, p)
                 nt_suite(chk, "h%d_grid%d" % (tile_h, grid), M, 512, K)
     chk.done()
 
 
 def test_gemm_nt_persistent_8phase_two_height_classes_in_one_launch():
     """nt_tile_h = 240: half the row tiles of each height.  The first class holds whole row tiles and a multiple of 8 tiles (`unit` in
-    gemm_nt_launch), so it is non-empty only from 8 column tiles on: M = 600, N = 2048 gives 8 tiles of 256 rows and 2 x 8 of 224."""
+    nt_plan), so it is non-empty only from 8 column tiles on: M = 600, N = 2048 gives 8 tiles of 256 rows and 2 x 8 of 224."""
     chk = Chk("gemm_nt.persistent8")
     with knobs(nt_big_min=1, nt_tile_h=240):
         assert nt_plan(600, 2048, 128)[0] == PERSISTENT
+        p = nt_launch_plan(600, 2048, 128)
+        assert (p["kernel"], p["tb"], p["tiles"], p["grid"]) == (K_NT8_TWO, 8, 24, 24), p
         nt_suite(chk, "h240", 600, 2048, 128)
     chk.done()
 
 
 @pytest.mark.parametrize("persistent", [0, 1])
 def test_gemm_nt_two_buffer_256_tile_kernel(persistent):
-    """gemm_nt8 = 0: the two-buffer 256 x 256 kernel, one workgroup per tile or persistent (gemm_nt_launch: the branch after the 8-phase one;
-    the plan names the family PERSISTENT for both, it cannot tell them apart)"""
+    """gemm_nt8 = 0: the two-buffer 256 x 256 kernel, one workgroup per tile or persistent (nt_plan: the branch after the 8-phase one).
+    avs_gemm_nt_plan names the family PERSISTENT for it and for the 8-phase kernels; avs_gemm_nt_launch_plan names the kernel."""
     chk = Chk("gemm_nt.twobuf256")
     with knobs(nt_big_min=1, gemm_nt8=0, gemm_persistent=persistent):
         for K in (64, 320):
             for M in (1, 255, 256, 257, 300, 600):
                 assert nt_plan(M, 512, K)[0] == PERSISTENT
+                p = nt_launch_plan(M, 512, K)
+                assert (p["kernel"], p["m_full"], p["grid"]) == (K_TWOBUF256, M, 2 * -(-M // 256)), (persistent, M, K, p)
                 nt_suite(chk, "persistent%d" % persistent, M, 512, K)
     chk.done()
 
