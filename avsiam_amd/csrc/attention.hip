@@ -1440,47 +1440,135 @@ __global__ __launch_bounds__(448, 1) void attn_bwd_fused224_kernel(AttnArgs a) {
 }
 
 // ===================================================================================================
-static int check_common(const char* name, const void* qkv, long long ld, int D, int H, int hd, const int* ts, const int* tl,
-                        const int* tq, int ntiles) {
-    if (!(qkv && ts && tl && tq && ntiles > 0 && H > 0 && (hd == 32 || hd == 64 || hd == 80) && D == H * hd && ld >= 3LL * D && (ld % 8) == 0)) {
-        avs_set_error("%s: bad arguments (D=%d H=%d hd=%d ld=%lld ntiles=%d)", name, D, H, hd, ld, ntiles);
-        return -2;
+// Host section.  attn_kernels is the ONE place where the runtime values (head dim, tile rows, "also write the 8-bit copy", the attn_ring knob)
+// become template arguments and where workgroup sizes and LDS bytes are written; attn_plan picks its entries by pure arithmetic; attn_launch
+// checks the arguments, asks the plan and launches what it says.  avs_attn_launch_plan exports the plan, so CPU tests pin the dispatch.
+enum AttnPass { ATTN_PASS_FWD = 0, ATTN_PASS_BWD = 1, ATTN_PASS_FUSED = 2 };      // forward | two-kernel backward (dQ, then dK/dV) | fused backward
+enum AttnFamily { AF_FWD = 0, AF_FWD_RING, AF_DQ, AF_DQ_RING, AF_DKV, AF_FUSED, AF_FUSED224, AF_COUNT };
+static const char* const attn_pass_name[3] = {"attn_fwd", "attn_bwd", "attn_bwd_fused"};                                    // in argument errors
+static const char* const attn_family_label[AF_COUNT] = {"attn_fwd", "attn_fwd", "attn_bwd_dq", "attn_bwd_dq", "attn_bwd_dkv", "attn_bwd_fused", "attn_bwd_fused224"};
+
+// The instantiation of family F at LDS image width W (32 | 64 | 96: head dim 80, the last 16 columns zero, five contraction steps), NW waves of
+// 32 rows and G8 (the backward's e5m2 copy; the forward takes its e4m3 copy at run time), or NULL where the file has none: no ring kernel at
+// width 96, the 224-row kernel at width 64 without the copy only, no 128-row fused kernel at width 96 (it would need 81 KB of LDS).
+template <int F, int W, int NW, bool G8>
+static const void* attn_fn() {
+    constexpr int HD = W == 96 ? 80 : W;
+    if constexpr (F == AF_FUSED224) { if constexpr (NW == 7 && W == 64 && !G8) return (const void*)attn_bwd_fused224_kernel; }
+    else if constexpr (NW == 7) return nullptr;
+    else if constexpr (F == AF_FWD) { if constexpr (!G8) return (const void*)attn_fwd_kernel<W, NW, HD>; }
+    else if constexpr (F == AF_FWD_RING) { if constexpr (W != 96 && !G8) return (const void*)attn_fwd_ring_kernel<W, NW, 3>; }
+    else if constexpr (F == AF_DQ) return (const void*)attn_bwd_dq_kernel<W, NW, HD, G8>;
+    else if constexpr (F == AF_DQ_RING) { if constexpr (W != 96) return (const void*)attn_bwd_dq_ring_kernel<W, NW, 3, G8>; }
+    else if constexpr (F == AF_DKV) return (const void*)attn_bwd_dkv_kernel<W, NW, HD, G8>;
+    else if constexpr (F == AF_FUSED) { if constexpr (W != 96 || NW == 2) return (const void*)attn_bwd_fused_kernel<W, NW, G8, HD>; }
+    return nullptr;
+}
+constexpr int ATTN_LDS224 = 3 * 224 * 64 * 2 + 224 * 128 * 2 + 2 * 224 * 4;      // the 224-row kernel's dynamic LDS: 145 152 bytes
+struct AttnRow { KernelEntry k[3][2]; };                     // [waves 2 | 4 | 7][g8]
+template <int F, int W, int NW, bool G8>
+static KernelEntry attn_entry() { return KernelEntry{attn_fn<F, W, NW, G8>(), F == AF_FUSED224 && NW == 7 ? ATTN_LDS224 : 0, 64 * NW}; }      // 128 | 256 | 448 threads
+template <int F, int W>
+static AttnRow attn_row() {
+    return AttnRow{{{attn_entry<F, W, 2, false>(), attn_entry<F, W, 2, true>()}, {attn_entry<F, W, 4, false>(), attn_entry<F, W, 4, true>()},
+                    {attn_entry<F, W, 7, false>(), attn_entry<F, W, 7, true>()}}};
+}
+struct AttnFamilyRows { AttnRow w[3]; };                     // [width 32 | 64 | 96]
+template <int F>
+static AttnFamilyRows attn_family() { return AttnFamilyRows{{attn_row<F, 32>(), attn_row<F, 64>(), attn_row<F, 96>()}}; }
+static const AttnFamilyRows attn_kernels[AF_COUNT] = {attn_family<AF_FWD>(), attn_family<AF_FWD_RING>(), attn_family<AF_DQ>(), attn_family<AF_DQ_RING>(),
+                                                      attn_family<AF_DKV>(), attn_family<AF_FUSED>(), attn_family<AF_FUSED224>()};
+static const KernelEntry& attn_kernel(int family, int width, int waves, int g8) { return attn_kernels[family].w[width / 32 - 1].k[waves / 2 - 1][g8 ? 1 : 0]; }
+
+// One or two dispatches (dQ, then dK/dV) of a call: pure arithmetic over the arguments and the attn_ring knob - no HIP call, no state.  rows: tile_rows /
+// rows_per_wg, g8: the call also writes the 8-bit copy, lq: AttnArgs::lq (the fused pass has none: ignored), items: ntiles / nseq.  n == 0: no such kernel (`why`).
+struct AttnDispatch { int family, width, waves, g8, grid, block, lds; };      // g8: the table's key (0 in the forward, whose kernels take the copy at run time)
+constexpr int ATTN_DISPATCH_FIELDS = sizeof(AttnDispatch) / sizeof(int);
+struct AttnPlan { int n; AttnDispatch d[2]; const char* why; };
+static AttnPlan attn_plan(int pass, int hd, int rows, int g8, int lq, int items, int H) {
+    AttnPlan p{0, {}, nullptr};
+    const bool fused = pass == ATTN_PASS_FUSED;
+    if (pass < ATTN_PASS_FWD || pass > ATTN_PASS_FUSED || !(hd == 32 || hd == 64 || hd == 80) || items <= 0 || H <= 0 || (!fused && lq < 0)) p.why = "bad arguments";
+    else if (!fused && rows != 64 && rows != 128) p.why = "tile_rows must be 64 or 128";
+    else if (rows != 64 && rows != 128 && rows != 224) p.why = "rows_per_wg must be 64, 128 or 224";
+    else if (rows == 224 && (hd != 64 || g8)) p.why = "224-row workgroups exist for head dim 64 without the e5m2 copy";
+    else if (fused && hd == 80 && rows != 64) p.why = "head dim 80 runs with 64-row workgroups only (a 128-row one needs 81 KB of LDS)";
+    if (p.why) return p;
+    const int width = hd == 80 ? 96 : hd, waves = rows / 32;
+    // K / V tiles by LDS-DMA ring (forward and dQ, hd 32 / 64, every row a query; bitwise the register-staged kernels' results)
+    const bool ring = avs_tuning().attn_ring != 0 && hd != 80 && lq == 0;
+    auto add = [&](int family, int g) {
+        p.d[p.n++] = AttnDispatch{family, width, waves, g, items * H, attn_kernel(family, width, waves, g).block, attn_kernel(family, width, waves, g).lds};
+    };
+    if (pass == ATTN_PASS_FWD) add(ring ? AF_FWD_RING : AF_FWD, 0);
+    else if (fused) add(rows == 224 ? AF_FUSED224 : AF_FUSED, g8 ? 1 : 0);
+    else { add(ring ? AF_DQ_RING : AF_DQ, g8 ? 1 : 0); add(AF_DKV, g8 ? 1 : 0); }
+    return p;
+}
+
+extern "C" int avs_attn_launch_plan(int pass, int hd, int rows, int g8, int lq, int items, int H, int* out, int n_out) {
+    AVS_CHECK_ARG(out && n_out > 0, "attn_launch_plan: bad arguments n_out=%d", n_out);
+    const AttnPlan p = attn_plan(pass, hd, rows, g8, lq, items, H);
+    AVS_CHECK_ARG(p.n > 0, "attn_launch_plan: %s (pass=%d hd=%d rows=%d g8=%d lq=%d items=%d H=%d)", p.why, pass, hd, rows, g8, lq, items, H);
+    const auto field = [&](const AttnDispatch& d, int j) { const int f[ATTN_DISPATCH_FIELDS] = {d.family, d.width, d.waves, d.g8, d.grid, d.block, d.lds}; return f[j]; };
+    for (int i = 0; i < n_out && i < 1 + p.n * ATTN_DISPATCH_FIELDS; ++i)
+        out[i] = i == 0 ? p.n : field(p.d[(i - 1) / ATTN_DISPATCH_FIELDS], (i - 1) % ATTN_DISPATCH_FIELDS);
+    return 0;
+}
+
+// The argument checks of every entry point (the combinations of hd / rows / copy that do not exist are attn_plan's).  Forward: out8 / ldo8 / q8
+// (all or none) also write e4m3(clamp(out * q8[0], +-448)) - the fp8 operand of the proj GEMM - and fold max |out| into q8[2].  Backward: dqkv8 /
+// ld8 / qd8 (all or none) also write e5m2(clamp(dqkv * qd8[0], +-57344)) [rows, 3*D] / ld8 - the gradient operand of the fp8 qkv input-gradient
+// GEMM - and fold max |dqkv| into the device record qd8; kv16 == 0 (with dqkv8 only): the key and value thirds of the bf16 dqkv are left
+// unwritten - their only readers take the e5m2 copy.
+static int attn_check(const char* name, int pass, const AttnArgs& a, int H, int hd) {
+    const bool fwd = pass == ATTN_PASS_FWD, fused = pass == ATTN_PASS_FUSED;
+    AVS_CHECK_ARG(a.lq >= 0, "%s: lq < 0", name);
+    AVS_CHECK_ARG(fwd || a.kv16 || a.dqkv8, "%s: kv_bf16 = 0 needs the e5m2 copy", name);
+    if (fwd) AVS_CHECK_ARG((a.out8 == nullptr) == (a.q8 == nullptr) && (!a.out8 || (a.ldo8 >= a.D && (a.ldo8 % 16) == 0)), "%s: out8 and q8 go together, ldo8 %% 16 == 0", name);
+    else AVS_CHECK_ARG((a.dqkv8 == nullptr) == (a.qd8 == nullptr) && (!a.dqkv8 || (a.ld8 >= 3LL * a.D && (a.ld8 % 16) == 0)), "%s: dqkv8 and its record go together, ld8 %% 16 == 0", name);
+    AVS_CHECK_ARG(a.qkv && a.tile_start && a.tile_len && (fused || a.tile_q0) && a.ntiles > 0 && H > 0 && (hd == 32 || hd == 64 || hd == 80) && a.D == H * hd &&
+                  a.ld >= 3LL * a.D && (a.ld % 8) == 0, "%s: bad arguments (D=%d H=%d hd=%d ld=%lld %s=%d)", name, a.D, H, hd, a.ld, fused ? "nseq" : "ntiles", a.ntiles);
+    if (fwd) AVS_CHECK_ARG(a.out && a.lse, "%s: null output", name);
+    else AVS_CHECK_ARG(a.out && a.dout && a.lse && (fused || a.delta) && a.dqkv && (!fused || (a.ldo % 8) == 0), "%s: null pointer", name);
+    if (!fused) AVS_CHECK_ARG((a.ldo % 8) == 0 && a.ldo >= a.D, "%s: ldo=%lld must be a multiple of 8 (%s) and >= D", name, a.ldo,
+                              fwd ? "the epilogue stores 16 bytes per lane" : "16-byte fragment loads of out / dO rows");
+    return 0;
+}
+
+static int attn_launch(int pass, AttnArgs a, int H, int rows, hipStream_t stream) {      // every entry point: check, plan, launch what the plan says (a.scale is set here)
+    const char* name = attn_pass_name[pass];
+    const int hd = H > 0 ? a.D / H : 0;
+    if (int e = attn_check(name, pass, a, H, hd)) return e;
+    const AttnPlan p = attn_plan(pass, hd, rows, pass == ATTN_PASS_FWD ? a.out8 != nullptr : a.dqkv8 != nullptr, a.lq, a.ntiles, H);
+    AVS_CHECK_ARG(p.n > 0, "%s: %s", name, p.why);
+    a.scale = 1.0f / sqrtf((float)hd);
+    for (int i = 0; i < p.n; ++i) {
+        const KernelEntry& k = attn_kernel(p.d[i].family, p.d[i].width, p.d[i].waves, p.d[i].g8);
+        static bool attr_done = false;          // the one entry with dynamic LDS (the 224-row kernel) asks for it at its first launch
+        if (k.lds > 0 && kernels_ready(name, attr_done, {{&k, 1}}) != 0) return -1;
+        kernel_launch(k, p.d[i].grid, a, stream);
+        AVS_LAUNCH_CHECK(attn_family_label[p.d[i].family]);
     }
     return 0;
 }
 
-// out8 / ldo8 / q8 (all or none): also write e4m3(clamp(out * q8[0], +-448)) - the fp8 operand of the proj GEMM - and fold max |out| into q8[2]
-static int attn_fwd_impl(const bf16_t* qkv, long long ld, int D, int H, const int* tile_start, const int* tile_len,
-                         const int* tile_q0, int ntiles, int tile_rows, bf16_t* out, long long ldo, float* lse, int rows_total,
-                         uint8_t* out8, long long ldo8, float* q8, int lq, hipStream_t stream) {
-    AVS_CHECK_ARG(lq >= 0, "attn_fwd: lq < 0");
-    AVS_CHECK_ARG((out8 == nullptr) == (q8 == nullptr) && (!out8 || (ldo8 >= D && (ldo8 % 16) == 0)), "attn_fwd: out8 and q8 go together, ldo8 %% 16 == 0");
-    AVS_CHECK_ARG(tile_rows == 128 || tile_rows == 64, "attn_fwd: tile_rows must be 64 or 128");
-    const int hd = H > 0 ? D / H : 0;
-    if (int e = check_common("attn_fwd", qkv, ld, D, H, hd, tile_start, tile_len, tile_q0, ntiles)) return e;
-    AVS_CHECK_ARG(out && lse, "attn_fwd: null output");
-    AVS_CHECK_ARG((ldo % 8) == 0 && ldo >= D, "attn_fwd: ldo=%lld must be a multiple of 8 (the epilogue stores 16 bytes per lane) and >= D", ldo);
-    AttnArgs a{qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, out, ldo, lse, rows_total, nullptr, nullptr, nullptr, 1.0f / sqrtf((float)hd),
-               out8, ldo8, q8, nullptr, 0, nullptr, 1, lq};
-    dim3 grid(ntiles * H);
-    // hd 80 (ViT-H: 1280 / 16 heads): a 96-wide LDS image whose last 16 columns are zero, five contraction steps
-    const bool ring = avs_tuning().attn_ring != 0 && lq == 0;          // K / V tiles by LDS-DMA ring (hd 32 / 64; bitwise the register-staged kernels' results)
-    if (hd == 80) { if (tile_rows == 128) attn_fwd_kernel<96, 4, 80><<<grid, 256, 0, stream>>>(a); else attn_fwd_kernel<96, 2, 80><<<grid, 128, 0, stream>>>(a); }
-    else if (tile_rows == 128) {
-        if (hd == 64) { if (ring) attn_fwd_ring_kernel<64, 4, 3><<<grid, 256, 0, stream>>>(a); else attn_fwd_kernel<64, 4><<<grid, 256, 0, stream>>>(a); }
-        else { if (ring) attn_fwd_ring_kernel<32, 4, 3><<<grid, 256, 0, stream>>>(a); else attn_fwd_kernel<32, 4><<<grid, 256, 0, stream>>>(a); }
-    } else {
-        if (hd == 64) { if (ring) attn_fwd_ring_kernel<64, 2, 3><<<grid, 128, 0, stream>>>(a); else attn_fwd_kernel<64, 2><<<grid, 128, 0, stream>>>(a); }
-        else { if (ring) attn_fwd_ring_kernel<32, 2, 3><<<grid, 128, 0, stream>>>(a); else attn_fwd_kernel<32, 2><<<grid, 128, 0, stream>>>(a); }
-    }
-    AVS_LAUNCH_CHECK("attn_fwd");
-    return 0;
+static AttnArgs attn_fwd_args(const bf16_t* qkv, long long ld, int D, const int* tile_start, const int* tile_len, const int* tile_q0, int ntiles, bf16_t* out,
+                              long long ldo, float* lse, int rows_total, uint8_t* out8, long long ldo8, float* q8, int lq) {
+    return AttnArgs{qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, out, ldo, lse, rows_total, nullptr, nullptr, nullptr, 0.f, out8, ldo8, q8, nullptr, 0, nullptr, 1, lq};
+}
+// (the fused pass: seq_start / seq_len as the tile arrays, no tile_q0, no delta, no lq)
+static AttnArgs attn_bwd_args(const bf16_t* qkv, long long ld, int D, const int* tile_start, const int* tile_len, const int* tile_q0, int ntiles, const bf16_t* out,
+                              const bf16_t* dout, long long ldo, const float* lse, float* delta, int rows_total, bf16_t* dqkv, uint8_t* dqkv8, long long ld8,
+                              float* qd8, int kv_bf16, int lq) {
+    return AttnArgs{qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, const_cast<bf16_t*>(out), ldo, const_cast<float*>(lse), rows_total, dout, delta, dqkv, 0.f,
+                    nullptr, 0, nullptr, dqkv8, ld8, qd8, kv_bf16, lq};
 }
 
 extern "C" int avs_attn_fwd_q8(const bf16_t* qkv, long long ld, int D, int H, const int* tile_start, const int* tile_len,
                                const int* tile_q0, int ntiles, int tile_rows, bf16_t* out, long long ldo, float* lse, int rows_total,
                                uint8_t* out8, long long ldo8, float* q8, hipStream_t stream) {
-    return attn_fwd_impl(qkv, ld, D, H, tile_start, tile_len, tile_q0, ntiles, tile_rows, out, ldo, lse, rows_total, out8, ldo8, q8, 0, stream);
+    return attn_launch(ATTN_PASS_FWD, attn_fwd_args(qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, out, ldo, lse, rows_total, out8, ldo8, q8, 0), H, tile_rows, stream);
 }
 
 // The same with only the first `lq` rows of every sequence as QUERIES (all rows are keys / values) and a COMPACT output: sequence s owns rows
@@ -1489,7 +1577,7 @@ extern "C" int avs_attn_fwd_cq(const bf16_t* qkv, long long ld, int D, int H, co
                                const int* tile_q0, int ntiles, int tile_rows, bf16_t* out, long long ldo, float* lse, int rows_total,
                                int lq, hipStream_t stream) {
     AVS_CHECK_ARG(lq > 0, "attn_fwd_cq: lq must be positive");
-    return attn_fwd_impl(qkv, ld, D, H, tile_start, tile_len, tile_q0, ntiles, tile_rows, out, ldo, lse, rows_total, nullptr, 0, nullptr, lq, stream);
+    return attn_launch(ATTN_PASS_FWD, attn_fwd_args(qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, out, ldo, lse, rows_total, nullptr, 0, nullptr, lq), H, tile_rows, stream);
 }
 
 extern "C" int avs_attn_fwd(const bf16_t* qkv, long long ld, int D, int H, const int* tile_start, const int* tile_len,
@@ -1498,63 +1586,12 @@ extern "C" int avs_attn_fwd(const bf16_t* qkv, long long ld, int D, int H, const
     return avs_attn_fwd_q8(qkv, ld, D, H, tile_start, tile_len, tile_q0, ntiles, tile_rows, out, ldo, lse, rows_total, nullptr, 0, nullptr, stream);
 }
 
-// dqkv8 / ld8 / qd8 (all or none): also write e5m2(clamp(dqkv * qd8[0], +-57344)) [rows, 3*D] / ld8 - the gradient operand of the fp8 qkv
-// input-gradient GEMM - and fold max |dqkv| into the device record qd8
-static int attn_bwd_impl(const bf16_t* qkv, long long ld, int D, int H, const int* tile_start, const int* tile_len,
-                         const int* tile_q0, int ntiles, int tile_rows, const bf16_t* out, const bf16_t* dout, long long ldo,
-                         const float* lse, float* delta, int rows_total, bf16_t* dqkv, uint8_t* dqkv8, long long ld8, float* qd8,
-                         int kv_bf16, int lq, hipStream_t stream) {
-    AVS_CHECK_ARG(lq >= 0, "attn_bwd: lq < 0");
-    // kv_bf16 == 0 (with dqkv8 only): the key and value thirds of the bf16 dqkv are left unwritten - their only readers take the e5m2 copy
-    AVS_CHECK_ARG(kv_bf16 || dqkv8, "attn_bwd: kv_bf16 = 0 needs the e5m2 copy");
-    AVS_CHECK_ARG((dqkv8 == nullptr) == (qd8 == nullptr) && (!dqkv8 || (ld8 >= 3LL * D && (ld8 % 16) == 0)), "attn_bwd: dqkv8 and its record go together, ld8 %% 16 == 0");
-    AVS_CHECK_ARG(tile_rows == 128 || tile_rows == 64, "attn_bwd: tile_rows must be 64 or 128");
-    const int hd = H > 0 ? D / H : 0;
-    if (int e = check_common("attn_bwd", qkv, ld, D, H, hd, tile_start, tile_len, tile_q0, ntiles)) return e;
-    AVS_CHECK_ARG(out && dout && lse && delta && dqkv, "attn_bwd: null pointer");
-    AVS_CHECK_ARG((ldo % 8) == 0 && ldo >= D, "attn_bwd: ldo=%lld must be a multiple of 8 (16-byte fragment loads of out / dO rows) and >= D", ldo);
-    AttnArgs a{qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, const_cast<bf16_t*>(out), ldo, const_cast<float*>(lse), rows_total,
-               dout, delta, dqkv, 1.0f / sqrtf((float)hd), nullptr, 0, nullptr, dqkv8, ld8, qd8, kv_bf16, lq};
-    dim3 grid(ntiles * H);
-#define ATTN_BWD2(K, G)                                                                                     \
-    do {                                                                                                    \
-        if (hd == 80) {                                                                                     \
-            if (tile_rows == 128) K<96, 4, 80, G><<<grid, 256, 0, stream>>>(a);                             \
-            else K<96, 2, 80, G><<<grid, 128, 0, stream>>>(a);                                              \
-        } else if (tile_rows == 128) {                                                                     \
-            if (hd == 64) K<64, 4, 64, G><<<grid, 256, 0, stream>>>(a);                                     \
-            else K<32, 4, 32, G><<<grid, 256, 0, stream>>>(a);                                              \
-        } else {                                                                                            \
-            if (hd == 64) K<64, 2, 64, G><<<grid, 128, 0, stream>>>(a);                                     \
-            else K<32, 2, 32, G><<<grid, 128, 0, stream>>>(a);                                              \
-        }                                                                                                   \
-    } while (0)
-    const bool ring = avs_tuning().attn_ring != 0 && hd != 80 && lq == 0;
-#define ATTN_BWD2R(K, G)                                                                                    \
-    do {                                                                                                    \
-        if (tile_rows == 128) {                                                                             \
-            if (hd == 64) K<64, 4, 3, G><<<grid, 256, 0, stream>>>(a);                                      \
-            else K<32, 4, 3, G><<<grid, 256, 0, stream>>>(a);                                               \
-        } else {                                                                                            \
-            if (hd == 64) K<64, 2, 3, G><<<grid, 128, 0, stream>>>(a);                                      \
-            else K<32, 2, 3, G><<<grid, 128, 0, stream>>>(a);                                               \
-        }                                                                                                   \
-    } while (0)
-    if (ring) { if (dqkv8) ATTN_BWD2R(attn_bwd_dq_ring_kernel, true); else ATTN_BWD2R(attn_bwd_dq_ring_kernel, false); }
-    else if (dqkv8) ATTN_BWD2(attn_bwd_dq_kernel, true); else ATTN_BWD2(attn_bwd_dq_kernel, false);
-#undef ATTN_BWD2R
-    AVS_LAUNCH_CHECK("attn_bwd_dq");
-    if (dqkv8) ATTN_BWD2(attn_bwd_dkv_kernel, true); else ATTN_BWD2(attn_bwd_dkv_kernel, false);
-#undef ATTN_BWD2
-    AVS_LAUNCH_CHECK("attn_bwd_dkv");
-    return 0;
-}
-
 extern "C" int avs_attn_bwd_q8(const bf16_t* qkv, long long ld, int D, int H, const int* tile_start, const int* tile_len,
                                const int* tile_q0, int ntiles, int tile_rows, const bf16_t* out, const bf16_t* dout, long long ldo,
                                const float* lse, float* delta, int rows_total, bf16_t* dqkv, uint8_t* dqkv8, long long ld8, float* qd8,
                                int kv_bf16, hipStream_t stream) {
-    return attn_bwd_impl(qkv, ld, D, H, tile_start, tile_len, tile_q0, ntiles, tile_rows, out, dout, ldo, lse, delta, rows_total, dqkv, dqkv8, ld8, qd8, kv_bf16, 0, stream);
+    return attn_launch(ATTN_PASS_BWD, attn_bwd_args(qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, out, dout, ldo, lse, delta, rows_total, dqkv, dqkv8, ld8, qd8, kv_bf16, 0),
+                       H, tile_rows, stream);
 }
 
 // The backward of avs_attn_fwd_cq: `out` / `dout` compact (sequence s owns rows s * lq ..), dq is written for the first lq rows of every
@@ -1563,7 +1600,8 @@ extern "C" int avs_attn_bwd_cq(const bf16_t* qkv, long long ld, int D, int H, co
                                const int* tile_q0, int ntiles, int tile_rows, const bf16_t* out, const bf16_t* dout, long long ldo,
                                const float* lse, float* delta, int rows_total, bf16_t* dqkv, int lq, hipStream_t stream) {
     AVS_CHECK_ARG(lq > 0, "attn_bwd_cq: lq must be positive");
-    return attn_bwd_impl(qkv, ld, D, H, tile_start, tile_len, tile_q0, ntiles, tile_rows, out, dout, ldo, lse, delta, rows_total, dqkv, nullptr, 0, nullptr, 1, lq, stream);
+    return attn_launch(ATTN_PASS_BWD, attn_bwd_args(qkv, ld, D, tile_start, tile_len, tile_q0, ntiles, out, dout, ldo, lse, delta, rows_total, dqkv, nullptr, 0, nullptr, 1, lq),
+                       H, tile_rows, stream);
 }
 
 extern "C" int avs_attn_bwd(const bf16_t* qkv, long long ld, int D, int H, const int* tile_start, const int* tile_len,
@@ -1573,51 +1611,12 @@ extern "C" int avs_attn_bwd(const bf16_t* qkv, long long ld, int D, int H, const
                            nullptr, 1, stream);
 }
 
-// One workgroup per (sequence, head) for sequences of at most `rows_per_wg` (64 or 128) tokens: seq_start / seq_len [nseq].
+// One workgroup per (sequence, head) for sequences of at most `rows_per_wg` (64, 128 or - head dim 64 - 224) tokens: seq_start / seq_len [nseq].
 extern "C" int avs_attn_bwd_fused_q8(const bf16_t* qkv, long long ld, int D, int H, const int* seq_start, const int* seq_len, int nseq,
                                      int rows_per_wg, const bf16_t* out, const bf16_t* dout, long long ldo, const float* lse, int rows_total,
                                      bf16_t* dqkv, uint8_t* dqkv8, long long ld8, float* qd8, int kv_bf16, hipStream_t stream) {
-    AVS_CHECK_ARG(kv_bf16 || dqkv8, "attn_bwd_fused: kv_bf16 = 0 needs the e5m2 copy");
-    AVS_CHECK_ARG((dqkv8 == nullptr) == (qd8 == nullptr) && (!dqkv8 || (ld8 >= 3LL * D && (ld8 % 16) == 0)), "attn_bwd_fused: dqkv8 and its record go together, ld8 %% 16 == 0");
-    AVS_CHECK_ARG(rows_per_wg == 64 || rows_per_wg == 128 || rows_per_wg == 224, "attn_bwd_fused: rows_per_wg must be 64, 128 or 224");
-    const int hd = H > 0 ? D / H : 0;
-    AVS_CHECK_ARG(qkv && seq_start && seq_len && nseq > 0 && H > 0 && (hd == 32 || hd == 64 || hd == 80) && D == H * hd && ld >= 3LL * D && (ld % 8) == 0,
-                  "attn_bwd_fused: bad arguments (D=%d H=%d hd=%d ld=%lld nseq=%d)", D, H, hd, ld, nseq);
-    AVS_CHECK_ARG(out && dout && lse && dqkv && (ldo % 8) == 0, "attn_bwd_fused: null pointer");
-    AVS_CHECK_ARG(rows_per_wg != 224 || (hd == 64 && !dqkv8), "attn_bwd_fused: 224-row workgroups exist for head dim 64 without the e5m2 copy");
-    AVS_CHECK_ARG(hd != 80 || rows_per_wg == 64, "attn_bwd_fused: head dim 80 runs with 64-row workgroups only (a 128-row one needs 81 KB of LDS)");
-    AttnArgs a{qkv, ld, D, seq_start, seq_len, nullptr, nseq, const_cast<bf16_t*>(out), ldo, const_cast<float*>(lse), rows_total,
-               dout, nullptr, dqkv, 1.0f / sqrtf((float)hd), nullptr, 0, nullptr, dqkv8, ld8, qd8, kv_bf16, 0};
-    dim3 grid(nseq * H);
-    if (rows_per_wg == 224) {
-        constexpr int SMEM224 = 3 * 224 * 64 * 2 + 224 * 128 * 2 + 2 * 224 * 4;
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute((const void*)attn_bwd_fused224_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM224) != hipSuccess) {
-                avs_set_error("attn_bwd_fused: cannot reserve %d bytes of LDS", SMEM224);
-                return -1;
-            }
-            attr_done = true;
-        }
-        attn_bwd_fused224_kernel<<<grid, 448, SMEM224, stream>>>(a);
-        AVS_LAUNCH_CHECK("attn_bwd_fused224");
-        return 0;
-    }
-#define ATTN_BWDF(G)                                                                                        \
-    do {                                                                                                    \
-        if (hd == 80) attn_bwd_fused_kernel<96, 2, G, 80><<<grid, 128, 0, stream>>>(a);                     \
-        else if (rows_per_wg == 128) {                                                                         \
-            if (hd == 64) attn_bwd_fused_kernel<64, 4, G><<<grid, 256, 0, stream>>>(a);                     \
-            else attn_bwd_fused_kernel<32, 4, G><<<grid, 256, 0, stream>>>(a);                              \
-        } else {                                                                                            \
-            if (hd == 64) attn_bwd_fused_kernel<64, 2, G><<<grid, 128, 0, stream>>>(a);                     \
-            else attn_bwd_fused_kernel<32, 2, G><<<grid, 128, 0, stream>>>(a);                              \
-        }                                                                                                   \
-    } while (0)
-    if (dqkv8) ATTN_BWDF(true); else ATTN_BWDF(false);
-#undef ATTN_BWDF
-    AVS_LAUNCH_CHECK("attn_bwd_fused");
-    return 0;
+    return attn_launch(ATTN_PASS_FUSED, attn_bwd_args(qkv, ld, D, seq_start, seq_len, nullptr, nseq, out, dout, ldo, lse, nullptr, rows_total, dqkv, dqkv8, ld8, qd8, kv_bf16, 0),
+                       H, rows_per_wg, stream);
 }
 
 extern "C" int avs_attn_bwd_fused(const bf16_t* qkv, long long ld, int D, int H, const int* seq_start, const int* seq_len, int nseq,

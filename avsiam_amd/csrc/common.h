@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 
 typedef uint16_t bf16_t;                                   // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;  // one MFMA A/B fragment (4 VGPRs)
@@ -126,6 +127,36 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ---- host-side launch tables (gemm.hip, attention.hip; the kernels with a fixed LDS size above 64 KiB elsewhere).  A file lists its kernel
+// instantiations once, each with the workgroup size and the dynamic LDS it runs in; the one-time attribute pass walks the tables and every
+// launch takes block and LDS from the entry it launches.
+struct KernelEntry { const void* fn; int lds, block; };     // kernel handle (NULL: the combination does not exist), dynamic LDS bytes, threads per workgroup
+struct KernelTable { const KernelEntry* k; int n; };
+
+// first call of an entry point (`done`: the caller's flag): every kernel of `tables` that takes dynamic LDS is allowed it (above 64 KiB a kernel
+// has to ask).  A failure returns -1 and leaves the pass to be tried again.
+static inline int kernels_ready(const char* who, bool& done, std::initializer_list<KernelTable> tables) {
+    if (done) return 0;
+    for (const KernelTable& t : tables)
+        for (int i = 0; i < t.n; ++i) {
+            if (!t.k[i].fn || t.k[i].lds <= 0) continue;
+            const hipError_t e = hipFuncSetAttribute(t.k[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, t.k[i].lds);
+            if (e != hipSuccess) {
+                avs_set_error("%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+                return -1;
+            }
+        }
+    done = true;
+    return 0;
+}
+
+// kernel<<<grid, k.block, k.lds, stream>>>(a) for a table entry (the call that statement compiles to; AVS_LAUNCH_CHECK picks up its error)
+template <class Args>
+static void kernel_launch(const KernelEntry& k, int grid, Args& a, hipStream_t stream) {
+    void* argv[1] = {&a};
+    (void)hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), argv, k.lds, stream);
+}
 
 // ---- process-wide tuning knobs (api.cpp).  Set ONLY through the C ABI (avs_tuning_set and the avs_gemm_set_* wrappers) - the host
 // binding reads the AVSIAM_* environment once at load and calls them; no launcher reads the environment or initialises anything

@@ -583,13 +583,8 @@ extern "C" int avs_resize_frames_u8(const uint8_t* in1, int Hs, int Ws, const in
     AVS_CHECK_ARG(rz_plan(ph, pw, out_h, out_w, &p) == 0, "resize_frames: %d x %d -> %d x %d: one output row takes more than %d bytes of LDS", ph, pw, out_h, out_w,
                   RZ_LDS_LIMIT);
     static bool attr_done = false;
-    if (!attr_done) {                                      // above the 64 KiB a kernel gets without asking
-        if (hipFuncSetAttribute((const void*)resize_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RZ_LDS_LIMIT) != hipSuccess) {
-            avs_set_error("resize_frames: hipFuncSetAttribute failed");
-            return -1;
-        }
-        attr_done = true;
-    }
+    static const KernelEntry kernel{(const void*)resize_frames_kernel, RZ_LDS_LIMIT, RZ_THREADS};      // above the 64 KiB a kernel gets without asking
+    if (int rc = kernels_ready("resize_frames", attr_done, {{&kernel, 1}})) return rc;
     const RzSrc A{in1, sizes, Hs, Ws, max_h, max_w, (size_t)n_images * 3 * Hs * Ws};
     const RzSrc B{in2, sizes2, Hs2, Ws2, max_h2, max_w2, in2 ? (size_t)n_images * 3 * Hs2 * Ws2 : 0};
     const RzGeo G{out_h, out_w, per_sample, p.rows, p.tcx, p.tcy, p.row_cap, p.sw, in2 ? 1 : 0};

@@ -1276,7 +1276,6 @@ extern "C" int avs_gemm_set_tile(int tile) { return avs_tuning_set("gemm_tile", 
 
 // Every GEMM kernel instantiation of this file with the dynamic LDS it runs in: the one-time hipFuncSetAttribute pass walks these tables
 // and every launch takes its LDS size from the entry it launches.  nt kernels by (act, NtKernel); an fp8 form the entry point refuses is NULL.
-struct GemmKernel { const void* fn; int lds, block; };      // kernel handle, dynamic LDS bytes, threads per workgroup
 enum NtKernel {                 // the first seven in the order avs_gemm_nt_launch_plan reports them
     NTK_TWOBUF128 = 0,          // gemm_nt_kernel<., 2, 4>      128 x 128 tiles, two buffers
     NTK_TWOBUF128_HALF,         //                              ... every row as 64 x 128 half-height tiles (m_full = 0)
@@ -1295,44 +1294,26 @@ static const void* nt8_fp8_kernel() {
     else return (const void*)gemm_nt8_kernel<ACT, FP8>;
 }
 template <int ACT>
-static const GemmKernel nt_kernels[NTK_COUNT] = {
+static const KernelEntry nt_kernels[NTK_COUNT] = {
     {(const void*)gemm_nt_kernel<ACT, 2, 4>, 65536, 256},       {(const void*)gemm_nt_kernel<ACT, 2, 4>, 65536, 256},
     {(const void*)gemm_nt_ring_kernel<ACT>, 131072, 256},       {(const void*)gemm_nt_ring_kernel<ACT, 2>, 98304, 256},
     {(const void*)gemm_nt_kernel<ACT, 4, 8>, 131072, 512},
     {(const void*)gemm_nt8_kernel<ACT, 0, 4, 4>, 131072, 512},  {(const void*)gemm_nt8_kernel<ACT, 0, 4, 3>, 131072, 512},
     {nt8_fp8_kernel<ACT, 1>(), 131072, 512},                    {nt8_fp8_kernel<ACT, 2>(), 131072, 512},
 };
-static const GemmKernel* const nt_kernels_by_act[3] = {nt_kernels<0>, nt_kernels<1>, nt_kernels<2>};      // the one place `act` becomes a template argument
+static const KernelEntry* const nt_kernels_by_act[3] = {nt_kernels<0>, nt_kernels<1>, nt_kernels<2>};      // the one place `act` becomes a template argument
 enum TnKernel { TNK_TWOBUF128 = 0, TNK_TWOBUF256, TNK_TN8, TNK_TN8_FP8, TNK_COUNT };
 struct GemmTn8Args;
 __global__ __launch_bounds__(512) void gemm_tn8f_kernel(GemmTn8Args g);      // (defined with the fp8 weight gradients below)
-static const GemmKernel tn_kernels[TNK_COUNT] = {
+static const KernelEntry tn_kernels[TNK_COUNT] = {
     {(const void*)gemm_tn_kernel<2, 2>, 65536, 256}, {(const void*)gemm_tn_kernel<4, 4>, 131072, 512}, {(const void*)gemm_tn8_kernel<0>, 131072, 512},
     {(const void*)gemm_tn8f_kernel, 98304, 512},
 };
 
-// first call of any GEMM entry point: every kernel above is allowed its dynamic LDS.  A failure leaves the pass to be tried again.
+// first call of any GEMM entry point: every kernel above is allowed its dynamic LDS (common.h kernels_ready)
 static int gemm_kernels_ready(const char* who) {
     static bool done = false;
-    if (done) return 0;
-    hipError_t e = hipSuccess;
-    const GemmKernel* const tables[4] = {nt_kernels<0>, nt_kernels<1>, nt_kernels<2>, tn_kernels};
-    for (int t = 0; t < 4; ++t)
-        for (int i = 0; i < (t < 3 ? NTK_COUNT : TNK_COUNT) && e == hipSuccess; ++i)
-            if (tables[t][i].fn) e = hipFuncSetAttribute(tables[t][i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, tables[t][i].lds);
-    if (e != hipSuccess) {
-        avs_set_error("%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
-        return -1;
-    }
-    done = true;
-    return 0;
-}
-
-// kernel<<<grid, k.block, k.lds, stream>>>(a) for a table entry (the call that statement compiles to; AVS_LAUNCH_CHECK picks up its error)
-template <class Args>
-static void gemm_launch(const GemmKernel& k, int grid, Args& a, hipStream_t stream) {
-    void* argv[1] = {&a};
-    (void)hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), argv, k.lds, stream);
+    return kernels_ready(who, done, {{nt_kernels<0>, NTK_COUNT}, {nt_kernels<1>, NTK_COUNT}, {nt_kernels<2>, NTK_COUNT}, {tn_kernels, TNK_COUNT}});
 }
 
 // Host-side plan of ONE dispatch of a forward / input-gradient GEMM: pure arithmetic over the shape, the knobs (gemm_tile, nt_big_min, gemm_ring,
@@ -1490,7 +1471,7 @@ static int nt_dispatch(GemmNtArgs a, hipStream_t stream) {
     const NtPlan p = nt_plan(a.M, a.N, a.K, a.m_split);
     a.tb = p.tb;
     a.m_full = p.m_full;
-    gemm_launch(nt_kernels_by_act[a.act][p.kernel], p.grid, a, stream);
+    kernel_launch(nt_kernels_by_act[a.act][p.kernel], p.grid, a, stream);
     AVS_LAUNCH_CHECK(p.kernel == NTK_NT8_ONE || p.kernel == NTK_NT8_TWO ? "gemm_nt8" : "gemm_nt");
     ++g_nt_dispatches;
     return 0;
@@ -1582,7 +1563,7 @@ extern "C" int avs_gemm_nt_fp8(const uint8_t* A, long long lda, const uint8_t* B
     a.out8 = out8; a.ldo8 = ldo8; a.out8_scale = out8_scale;
     a.qa = qa; a.qw = qw; a.qw2 = dual ? qw2 : qw; a.q8 = q8;
     a.aux8 = (out_gp8 || aux_gp8) ? 1 : 0;
-    gemm_launch(nt_kernels_by_act[act][a_e5m2 ? NTK_FP8_DGRAD : NTK_FP8], nt_persistent_grid(ceil_div(M, 256) * (N / 256)), a, stream);
+    kernel_launch(nt_kernels_by_act[act][a_e5m2 ? NTK_FP8_DGRAD : NTK_FP8], nt_persistent_grid(ceil_div(M, 256) * (N / 256)), a, stream);
     AVS_LAUNCH_CHECK("gemm_nt_fp8");
     return 0;
 }
@@ -1675,9 +1656,9 @@ extern "C" int avs_gemm_tn_bf16(const bf16_t* A, long long lda, const bf16_t* B,
         GemmTnGroupArgs g{};
         g.p[0] = TnProb{A, lda, B, ldb, C, ldc, N1, N2, 0};
         g.nprob = 1; g.tiles = pl.tiles; g.M = M; g.stages_per_split = pl.stages_per_split;
-        gemm_launch(tn_kernels[TNK_TN8], grid, g, stream);
+        kernel_launch(tn_kernels[TNK_TN8], grid, g, stream);
     }
-    else gemm_launch(tn_kernels[big ? TNK_TWOBUF256 : TNK_TWOBUF128], grid, a, stream);
+    else kernel_launch(tn_kernels[big ? TNK_TWOBUF256 : TNK_TWOBUF128], grid, a, stream);
     AVS_LAUNCH_CHECK("gemm_tn");
     return 0;
 }
@@ -1863,7 +1844,7 @@ extern "C" int avs_gemm_tn_fp8_group3(const uint8_t* A0, long long lda0, const u
     if (gemm_kernels_ready("gemm_tn_fp8_group3") != 0) return -1;
     const TnPlan pl = tn_group_plan(M, tiles, 1.0);
     g.nprob = n; g.tiles = tiles; g.M = M; g.stages_per_split = pl.stages_per_split;
-    gemm_launch(tn_kernels[TNK_TN8_FP8], tiles * pl.splits, g, stream);
+    kernel_launch(tn_kernels[TNK_TN8_FP8], tiles * pl.splits, g, stream);
     AVS_LAUNCH_CHECK("gemm_tn_fp8_group3");
     return 0;
 }
@@ -1898,7 +1879,7 @@ extern "C" int avs_gemm_tn_bf16_group3(const bf16_t* A0, long long lda0, const b
     if (gemm_kernels_ready("gemm_tn_group3") != 0) return -1;
     const TnPlan pl = tn_group_plan(M, tiles, 1.3);
     g.nprob = n; g.tiles = tiles; g.M = M; g.stages_per_split = pl.stages_per_split;
-    gemm_launch(tn_kernels[TNK_TN8], tiles * pl.splits, g, stream);
+    kernel_launch(tn_kernels[TNK_TN8], tiles * pl.splits, g, stream);
     AVS_LAUNCH_CHECK("gemm_tn_group3");
     return 0;
 }

@@ -216,13 +216,8 @@ extern "C" int avs_resample_wave(const float* wave, int B, int C, long long stri
     const int span_off = (max_words + 3) & ~3;
     const size_t lds = (size_t)(span_off + max_span) * 4;
     static bool attr_done = false;
-    if (!attr_done) {                                          // above the 64 KiB a kernel gets without asking
-        if (hipFuncSetAttribute((const void*)resample_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_LIMIT) != hipSuccess) {
-            avs_set_error("resample_wave: hipFuncSetAttribute failed");
-            return -1;
-        }
-        attr_done = true;
-    }
+    static const KernelEntry kernel{(const void*)resample_wave_kernel, RS_LDS_LIMIT, RS_THREADS};      // above the 64 KiB a kernel gets without asking
+    if (int rc = kernels_ready("resample_wave", attr_done, {{&kernel, 1}})) return rc;
     const int vec_ok = (stride % 4 == 0) && (reinterpret_cast<uintptr_t>(wave) & 15) == 0;
     dim3 grid((unsigned)((out_stride + RS_TILE - 1) / RS_TILE), B);
     resample_wave_kernel<<<grid, RS_THREADS, lds, stream>>>(wave, C, (int)stride, len, tab_idx, tabs, out, (int)out_stride, out_len, span_off, vec_ok);

@@ -16,6 +16,7 @@ MI355X-first restructuring of ``CAVMAE_BASE.forward`` (/root/reference/src/model
 
 The mask plan (which tokens each sample keeps) is an explicit input - see maskplan.py.
 """
+import collections
 import math
 import os
 
@@ -289,6 +290,45 @@ def fp8_applies(opts, D, hidden):
     return opts.fp8 in ("1", "2", "3") and D % 256 == 0 and hidden % 256 == 0 and D >= 256
 
 
+# what a stack's attention runs with: forward tile rows, the (lo, hi] length classes of the fused backward that hold at least one sequence, the
+# length above which a sequence takes the two-kernel backward, and that backward's tile rows
+AttentionPlan = collections.namedtuple("AttentionPlan", "fwd_rows fused cut bwd_rows")
+
+
+def attention_plan(seq_lens, hd, *, attn_tile, attn_fused, fused224, inference):
+    """The attention kernels' tiling for a packed batch of sequences at head dim `hd` (no device involved): Stack._select_attention builds its
+    tile tables from this, tools/bench_attn.py its step mixes.  attn_tile / attn_fused: EngineOptions; fused224: whether the 7-wave fused
+    backward may be selected (Stack._fused224); inference: no backward (bwd_rows = fwd_rows, no fused class)."""
+    # rows per attention workgroup (4 or 2 waves of 32 queries / keys), by the mean sequence length of the stack - measured on the
+    # step's mixes (tools/bench_attn.py --step): the backward of the contrastive pass (39-196 video, 102-512 audio tokens) is 12 %
+    # faster with 64-row workgroups, its forward 11 % slower; 49/128-token towers: forward 10 % faster; 618 and 2472 tokens: 128
+    mean_len = sum(seq_lens) / max(1, len(seq_lens))
+    force = int(attn_tile)                                                # A/B switch: 64 | 128 for every stack and direction
+    if hd == 80 and not force:
+        force = 128                                                       # hd 80 (ViT-H): the 64-row instantiations exist and lose (round 6, tools/bench_attn.py --huge --tile64:
+                                                                          # backward +25 % on the contrastive mix - 232-256 registers, the dK/dV kernel spills)
+    fwd_rows = force or (64 if mean_len < 64 else 128)
+    if inference:
+        return AttentionPlan(fwd_rows, [], 0, fwd_rows)
+    # backward: sequences that fit one workgroup (<= 64 / <= 128 tokens: the encoder's video sequences, the MAE towers) take the
+    # fused kernel (one read of q, k, v, o, dO and one S / exp evaluation for dq, dk and dv; ops.attn_bwd_fused), the longer ones the
+    # two-kernel form.  AVSIAM_ATTN_FUSED=0: everything through the two kernels (A/B).
+    # (head dim 80 has the 64-row fused form only - a 128-row workgroup would need 81 KB of LDS: the MAE towers' 64-token frame sequences and the
+    #  contrastive pass's 51-token ones; -27 % / -2 % on those stacks' backward attention, tools/bench_attn.py --huge)
+    cut = 0 if not attn_fused else {32: 128, 64: 128, 80: 64}.get(hd, 0)
+    fused = []
+    if cut:
+        fused = [(lo, hi) for lo, hi in ((0, 64), (64, cut)) if any(lo < L <= hi for L in seq_lens)]
+        # round 6: sequences of 129 .. 224 tokens at head dim 64 (the encoder's 156 / 196-token frames, 204-token audio) in one 7-wave workgroup
+        # per (sequence, head) whose dS image holds the queries in two halves (attn_bwd_fused224_kernel)
+        if hd == 64 and fused224 and any(128 < L <= 224 for L in seq_lens):
+            fused.append((128, 224))
+            cut = 224
+    long_lens = [L for L in seq_lens if L > cut]
+    mean_long = sum(long_lens) / max(1, len(long_lens))
+    return AttentionPlan(fwd_rows, fused, cut, force or (64 if mean_long < 256 else 128))
+
+
 def make_stack(dev, rows, D, H, hidden, seq_lens, blocks, row_mod=None, *, blocks2=None, split=0, inference=False, pool=None, opts=None, q_rows=0):
     """The stack every pass builds (arguments: Stack.__init__): an engine_fp8.Fp8Stack where fp8_applies(), else the bf16 Stack."""
     opts = opts if opts is not None else EngineOptions.from_env()
@@ -393,39 +433,12 @@ class Stack:
         self._setup_pruned(q_rows, seq_lens, dev)
 
     def _select_attention(self, seq_lens, dev):
-        """tile tables of the attention kernels: self.tiles (forward), self.fused_bwd / self.tiles_bwd (backward)"""
-        opts, rows, D, H, inference = self.opts, self.rows, self.D, self.H, self.inference
-        # rows per attention workgroup (4 or 2 waves of 32 queries / keys), by the mean sequence length of the stack - measured on the
-        # step's mixes (tools/bench_attn.py --step): the backward of the contrastive pass (39-196 video, 102-512 audio tokens) is 12 %
-        # faster with 64-row workgroups, its forward 11 % slower; 49/128-token towers: forward 10 % faster; 618 and 2472 tokens: 128
-        mean_len = rows / max(1, len(seq_lens))
-        force = int(opts.attn_tile)                                           # A/B switch: 64 | 128 for every stack and direction
-        if D // H == 80 and not force:
-            force = 128                                                       # hd 80 (ViT-H): the 64-row instantiations exist and lose (round 6, tools/bench_attn.py --huge --tile64:
-                                                                              # backward +25 % on the contrastive mix - 232-256 registers, the dK/dV kernel spills)
-        self.tiles = ops.AttnTiles(seq_lens, dev, tile_rows=force or (64 if mean_len < 64 else 128))
-        # backward: sequences that fit one workgroup (<= 64 / <= 128 tokens: the encoder's video sequences, the MAE towers) take the
-        # fused kernel (one read of q, k, v, o, dO and one S / exp evaluation for dq, dk and dv; ops.attn_bwd_fused), the longer ones the
-        # two-kernel form.  AVSIAM_ATTN_FUSED=0: everything through the two kernels (A/B).
-        self.fused_bwd = []
-        if inference:
-            self.tiles_bwd = self.tiles
-        else:
-            # (head dim 80 has the 64-row fused form only - a 128-row workgroup would need 81 KB of LDS: the MAE towers' 64-token frame sequences and the
-            #  contrastive pass's 51-token ones; -27 % / -2 % on those stacks' backward attention, tools/bench_attn.py --huge)
-            cut = 0 if not opts.attn_fused else {32: 128, 64: 128, 80: 64}.get(D // H, 0)
-            if cut:
-                self.fused_bwd = [sq for sq in (ops.AttnSeqs(seq_lens, dev, 0, 64), ops.AttnSeqs(seq_lens, dev, 64, cut)) if sq.nseq]
-                # round 6: sequences of 129 .. 224 tokens at head dim 64 (the encoder's 156 / 196-token frames, 204-token audio) in one 7-wave workgroup
-                # per (sequence, head) whose dS image holds the queries in two halves (attn_bwd_fused224_kernel)
-                if D // H == 64 and self._fused224():
-                    big = ops.AttnSeqs(seq_lens, dev, 128, 224)
-                    if big.nseq:
-                        self.fused_bwd.append(big)
-                        cut = 224
-            long_lens = [L for L in seq_lens if L > cut]
-            mean_long = sum(long_lens) / max(1, len(long_lens))
-            self.tiles_bwd = ops.AttnTiles(seq_lens, dev, tile_rows=force or (64 if mean_long < 256 else 128), min_len=cut)
+        """tile tables of the attention kernels (attention_plan): self.tiles (forward), self.fused_bwd / self.tiles_bwd (backward)"""
+        plan = attention_plan(seq_lens, self.D // self.H, attn_tile=self.opts.attn_tile, attn_fused=self.opts.attn_fused, fused224=self._fused224(),
+                              inference=self.inference)
+        self.tiles = ops.AttnTiles(seq_lens, dev, tile_rows=plan.fwd_rows)
+        self.fused_bwd = [ops.AttnSeqs(seq_lens, dev, lo, hi) for lo, hi in plan.fused]
+        self.tiles_bwd = self.tiles if self.inference else ops.AttnTiles(seq_lens, dev, tile_rows=plan.bwd_rows, min_len=plan.cut)
 
     def _setup_pruned(self, q_rows, seq_lens, dev):
         """the pruned last block (Stack.__init__, q_rows): sets self.lq and the row maps where the form applies"""

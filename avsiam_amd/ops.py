@@ -510,27 +510,21 @@ def attn_q_scale(hd):
 def attn_fwd(qkv, tiles, H, out, lse, out8=None, q8=None, lq=0):
     """out8 / q8 (fp8 mode): also write the e4m3 copy of the output for the proj GEMM, scaled by the device record q8.
     lq > 0 (equal-length sequences; avs_attn_fwd_cq): only the first lq rows of every sequence are queries, `out` is compact
-    (sequence s owns rows s * lq ..) - the decoder's last block in the pruned form (engine.Stack)."""
-    if lq:
-        assert out8 is None and tiles.uniform_len and 0 < lq <= tiles.uniform_len
-        _chk(qkv, BF16, "attn.qkv", 2); _chk(out, BF16, "attn.out", 2); _chk(lse, F32, "attn.lse", 2)
-        D = qkv.shape[1] // 3
-        nseq = tiles.max_row // tiles.uniform_len
-        assert qkv.shape[1] == 3 * D and out.shape[1] == D and D % H == 0 and D // H in (32, 64, 80)
-        assert qkv.shape[0] >= tiles.max_row and out.shape[0] >= nseq * lq and lse.shape[0] == H and lse.shape[1] >= tiles.max_row
-        frac = lq / tiles.uniform_len
-        _launch("attn_fwd_hd%d" % (D // H), (4.0 * tiles.sum_sq * frac * D, tiles.rows * ((4.0 + 4.0 * frac) * D + 4.0 * H * frac)), "avs_attn_fwd_cq", qkv, qkv.stride(0), D, H,
-                tiles.start, tiles.len, tiles.q0, tiles.ntiles, tiles.tile_rows, out, out.stride(0), lse, lse.shape[1], int(lq), _stream())
-        return
+    (sequence s owns rows s * lq ..) - the decoder's last block in the pruned form (engine.Stack).  That form differs in the rows `out`
+    must hold, in the work estimate (the query fraction) and in the entry point."""
     _chk(qkv, BF16, "attn.qkv", 2); _chk(out, BF16, "attn.out", 2); _chk(lse, F32, "attn.lse", 2); _chk(out8, U8, "attn.out8", 2)
     assert (out8 is None) == (q8 is None) and (out8 is None or (out8.shape[0] >= tiles.max_row and out8.shape[1] == out.shape[1]))
+    assert not lq or (out8 is None and tiles.uniform_len and 0 < lq <= tiles.uniform_len)
     D = qkv.shape[1] // 3
     assert qkv.shape[1] == 3 * D and out.shape[1] == D and D % H == 0 and D // H in (32, 64, 80)
-    assert qkv.shape[0] >= tiles.max_row and out.shape[0] >= tiles.max_row
+    assert qkv.shape[0] >= tiles.max_row and out.shape[0] >= (tiles.max_row // tiles.uniform_len * lq if lq else tiles.max_row)
     assert lse.shape[0] == H and lse.shape[1] >= tiles.max_row
+    frac = lq / tiles.uniform_len if lq else 1.0
     # algorithmic HBM bytes: q, k, v read and o written once per row (bf16), lse written per head and row
-    _launch("attn_fwd_hd%d" % (D // H), (4.0 * tiles.sum_sq * D, tiles.rows * (8.0 * D + 4.0 * H)), "avs_attn_fwd_q8", qkv, qkv.stride(0), D, H, tiles.start, tiles.len, tiles.q0, tiles.ntiles, tiles.tile_rows, out, out.stride(0),
-            lse, lse.shape[1], out8, out8.stride(0) if out8 is not None else 0, _qrec(q8), _stream())
+    cost = (4.0 * tiles.sum_sq * frac * D, tiles.rows * ((4.0 + 4.0 * frac) * D + 4.0 * H * frac))
+    tail = (int(lq),) if lq else (out8, out8.stride(0) if out8 is not None else 0, _qrec(q8))
+    _launch("attn_fwd_hd%d" % (D // H), cost, "avs_attn_fwd_cq" if lq else "avs_attn_fwd_q8", qkv, qkv.stride(0), D, H, tiles.start, tiles.len, tiles.q0, tiles.ntiles,
+            tiles.tile_rows, out, out.stride(0), lse, lse.shape[1], *tail, _stream())
 
 
 def attn_bwd(qkv, tiles, H, out, dout, lse, delta, dqkv, dqkv8=None, q8=None, kv_bf16=True, lq=0):
@@ -539,29 +533,22 @@ def attn_bwd(qkv, tiles, H, out, dout, lse, delta, dqkv, dqkv8=None, q8=None, kv
     the bf16 dqkv are not written.
     lq > 0 (avs_attn_bwd_cq): the backward of attn_fwd(lq=): out / dout compact, dq written for the first lq rows of every sequence only."""
     assert kv_bf16 or dqkv8 is not None
-    if lq:
-        assert dqkv8 is None and tiles.uniform_len and 0 < lq <= tiles.uniform_len
-        _chk(qkv, BF16, "attnb.qkv", 2); _chk(out, BF16, "attnb.out", 2); _chk(dout, BF16, "attnb.dout", 2)
-        _chk(lse, F32, "attnb.lse", 2); _chk(delta, F32, "attnb.delta", 2); _chk(dqkv, BF16, "attnb.dqkv", 2)
-        D = qkv.shape[1] // 3
-        nseq = tiles.max_row // tiles.uniform_len
-        assert dqkv.shape == qkv.shape and out.shape[1] == D and dout.shape == out.shape and delta.shape == lse.shape and D // H in (32, 64, 80)
-        assert qkv.shape[0] >= tiles.max_row and out.shape[0] >= nseq * lq and lse.shape[0] == H and lse.shape[1] >= tiles.max_row
-        frac = lq / tiles.uniform_len
-        _launch("attn_bwd_hd%d" % (D // H), (8.0 * tiles.sum_sq * frac * D, tiles.rows * ((16.0 + 8.0 * frac) * D + 16.0 * H * frac)), "avs_attn_bwd_cq", qkv, qkv.stride(0), D, H,
-                tiles.start, tiles.len, tiles.q0, tiles.ntiles, tiles.tile_rows, out, dout, out.stride(0), lse, delta, lse.shape[1], dqkv, int(lq), _stream())
-        return
     _chk(qkv, BF16, "attnb.qkv", 2); _chk(out, BF16, "attnb.out", 2); _chk(dout, BF16, "attnb.dout", 2); _chk(dqkv8, U8, "attnb.dqkv8", 2)
     assert (dqkv8 is None) == (q8 is None) and (dqkv8 is None or (dqkv8.shape[0] >= tiles.max_row and dqkv8.shape[1] == qkv.shape[1]))
+    assert not lq or (dqkv8 is None and tiles.uniform_len and 0 < lq <= tiles.uniform_len)
     _chk(lse, F32, "attnb.lse", 2); _chk(delta, F32, "attnb.delta", 2); _chk(dqkv, BF16, "attnb.dqkv", 2)
     D = qkv.shape[1] // 3
     assert dqkv.shape == qkv.shape and out.shape[1] == D and dout.shape == out.shape and delta.shape == lse.shape and D // H in (32, 64, 80)
-    assert qkv.shape[0] >= tiles.max_row and out.shape[0] >= tiles.max_row and lse.shape[0] == H and lse.shape[1] >= tiles.max_row
+    assert qkv.shape[0] >= tiles.max_row and out.shape[0] >= (tiles.max_row // tiles.uniform_len * lq if lq else tiles.max_row)
+    assert lse.shape[0] == H and lse.shape[1] >= tiles.max_row
+    frac = lq / tiles.uniform_len if lq else 1.0
     # algorithmic FLOP: 8 * sum L^2 * D - the four products of the backward (dV, dP, dQ, dK); the recomputation of S = Q.K^T that the
     # kernels pay instead of keeping an L x L tensor is NOT counted (SURVEY.md 8(d)).  Algorithmic HBM bytes of the two kernels: dQ
     # reads q, k, v, o, dO and writes dq (+ delta); dK/dV reads q, k, v, dO and writes dk, dv
-    _launch("attn_bwd_hd%d" % (D // H), (8.0 * tiles.sum_sq * D, tiles.rows * (24.0 * D + 16.0 * H)), "avs_attn_bwd_q8", qkv, qkv.stride(0), D, H, tiles.start, tiles.len, tiles.q0, tiles.ntiles, tiles.tile_rows, out, dout,
-            out.stride(0), lse, delta, lse.shape[1], dqkv, dqkv8, dqkv8.stride(0) if dqkv8 is not None else 0, _qrec(q8), 1 if kv_bf16 else 0, _stream())
+    cost = (8.0 * tiles.sum_sq * frac * D, tiles.rows * ((16.0 + 8.0 * frac) * D + 16.0 * H * frac))
+    tail = (int(lq),) if lq else (dqkv8, dqkv8.stride(0) if dqkv8 is not None else 0, _qrec(q8), 1 if kv_bf16 else 0)
+    _launch("attn_bwd_hd%d" % (D // H), cost, "avs_attn_bwd_cq" if lq else "avs_attn_bwd_q8", qkv, qkv.stride(0), D, H, tiles.start, tiles.len, tiles.q0, tiles.ntiles,
+            tiles.tile_rows, out, dout, out.stride(0), lse, delta, lse.shape[1], dqkv, *tail, _stream())
 
 
 class AttnSeqs:

@@ -256,6 +256,20 @@ int avs_attn_bwd_fused(const avs_bf16* qkv, long long ld, int D, int H, const in
 int avs_attn_bwd_fused_q8(const avs_bf16* qkv, long long ld, int D, int H, const int* seq_start, const int* seq_len, int nseq,
                           int rows_per_wg, const avs_bf16* out, const avs_bf16* dout, long long ldo, const float* lse, int rows_total,
                           avs_bf16* dqkv, uint8_t* dqkv8, long long ld8, float* qd8, int kv_bf16, avs_stream_t stream);
+/* The launches an attention entry point makes under the current knobs (attn_ring) - the plan the launcher itself consumes.
+ *   pass   which entry points: the forward (avs_attn_fwd / _q8 / _cq), the two-kernel backward (avs_attn_bwd / _q8 / _cq) or the fused one
+ *   hd     head dim 32 | 64 | 80         rows   tile_rows / rows_per_wg          g8   the call also writes the 8-bit copy (out8 / dqkv8)
+ *   lq     0, or the _cq forms' query rows per sequence (the fused pass has none: ignored)      items   ntiles / nseq      H   heads
+ * Writes out[0] = number of dispatches (1; 2 for the two-kernel backward: dQ, then dK/dV), then per dispatch, in this order:
+ *   family   enum avs_attn_family         width   LDS image width 32 | 64 | 96 (head dim 80)        waves   2 | 4 | 7 (32 rows each)
+ *   g8       the kernel is the form that writes the 8-bit copy (0 in the forward: its kernels take the copy at run time)
+ *   grid     workgroups = items * H       block   threads per workgroup                             lds     dynamic LDS bytes
+ * A shorter array receives the leading fields only.  -2 for a combination the entry points refuse: head dim 80 fused above 64 rows, 224 rows
+ * with head dim != 64 or with the 8-bit copy or outside the fused pass, any other rows / hd.  Host arithmetic only (callable without a GPU). */
+enum avs_attn_pass { AVS_ATTN_PASS_FWD = 0, AVS_ATTN_PASS_BWD = 1, AVS_ATTN_PASS_FUSED = 2 };
+enum avs_attn_family { AVS_ATTN_FWD = 0, AVS_ATTN_FWD_RING = 1, AVS_ATTN_DQ = 2, AVS_ATTN_DQ_RING = 3, AVS_ATTN_DKV = 4, AVS_ATTN_FUSED = 5,
+                       AVS_ATTN_FUSED224 = 6 };
+int avs_attn_launch_plan(int pass, int hd, int rows, int g8, int lq, int items, int H, int* out, int n_out);
 
 /* ---- input normalisation on the device (what the reference dataloader does per sample on the host: dataloader.py:505-513
  * fbank = (fbank - norm_mean) / norm_std [+ rand * amp, roll(shift) when `noise`]; :461-462,152-155 frame / 255 then

@@ -17,7 +17,8 @@ from tests import exactlib as X
 from tests import fp8lib as fl
 from tests import rowwise as rw
 from tests.test_fp8_exact_gpu import BF8_MAX, check_codes, records
-from tests.test_rowwise_gpu import Chk, _attn_buffers, knobs, ops
+from tests.test_rowwise_gpu import (A_FUSED, A_FUSED224, PASS_BWD, PASS_FUSED, PASS_FWD, Chk, _attn_buffers, attn_meant, attn_reached, knobs,
+                                    ops)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,7 +77,7 @@ def _forward(hd, profile, tile_rows=128):
 
 
 # ===================================================================================================
-TWO_KERNEL = [(32, 64), (32, 128), (64, 64), (64, 128), (80, 64), (80, 128)]      # (the dispatch has 64-row instances of head dim 80: attn_fwd_impl / attn_bwd_impl)
+TWO_KERNEL = [(32, 64), (32, 128), (64, 64), (64, 128), (80, 64), (80, 128)]      # (the kernel table has 64-row instances of head dim 80)
 
 
 @pytest.mark.parametrize("profile", rw.ATTN_PROFILES)
@@ -93,6 +94,7 @@ def test_two_kernel_forward_and_backward(hd, tile_rows, profile):
     for ring in ((0,) if hd == 80 else (0, 1)):               # (head dim 80 has no ring form)
         qkv, dout, out, lse = _attn_buffers(c, LENS, H, hd, ROWS)
         with knobs(attn_ring=ring):
+            assert (attn_reached(PASS_FWD, tiles, H, hd), attn_reached(PASS_BWD, tiles, H, hd)) == attn_meant(hd, tile_rows, ring)
             o.attn_fwd(qkv, tiles, H, out, lse)
             dqkv = torch.full_like(qkv, rw.SENTINEL[BF])
             delta = torch.full_like(lse, rw.SENTINEL[F32])
@@ -122,6 +124,7 @@ def test_fused_backward_length_classes(hd, profile):
     for lo, hi in FUSED_CLASSES[hd]:
         sq = o.AttnSeqs(list(LENS), DEV, lo, hi)
         assert sq.nseq == sum(1 for L in LENS if lo < L <= hi) > 0
+        assert attn_reached(PASS_FUSED, sq, H, hd) == [(A_FUSED224 if hi == 224 else A_FUSED, 96 if hd == 80 else hd, hi // 32, 0)]
         dqkv = torch.full_like(qkv, rw.SENTINEL[BF])
         o.attn_bwd_fused(qkv, sq, H, out, dout, lse, dqkv)
         mine = (seq_len > lo) & (seq_len <= hi)
@@ -144,6 +147,7 @@ def test_compact_queries(hd, lq, profile):
     chk = Chk("attn_peaked.cq.hd%d" % hd)
     qkv, dout, out, lse = _attn_buffers(c, LENS_CQ, H, hd, nq)
     tiles = o.AttnTiles(list(LENS_CQ), DEV, tile_rows=128)
+    assert (attn_reached(PASS_FWD, tiles, H, hd, lq=lq), attn_reached(PASS_BWD, tiles, H, hd, lq=lq)) == attn_meant(hd, 128)
     o.attn_fwd(qkv, tiles, H, out, lse, lq=lq)
     dqkv = torch.full_like(qkv, rw.SENTINEL[BF])
     delta = torch.full_like(lse, rw.SENTINEL[F32])
@@ -182,11 +186,18 @@ def test_fp32_forward(hd, profile):
 # (h) the backward's e5m2 copy of dqkv (fp8 modes 2 and 3: the operand of the fp8 qkv input-gradient GEMM)
 @pytest.mark.parametrize("profile", ["randn", "sharp"])
 @pytest.mark.parametrize("hd", [32, 64, 80])
-@pytest.mark.parametrize("form", ["two_kernel", "fused"])
+@pytest.mark.parametrize("form", ["two_kernel", "fused", "two_kernel_ring", "two_kernel_64_ring"])
 def test_backward_e5m2_copy(form, hd, profile):
     """dqkv8 beside the bf16 dqkv, kv_bf16 1 and 0: the bf16 gradients bitwise those of the plain call (kv_bf16 = 0: the query third, the key / value
     thirds unwritten), every byte of the copy inside the rounding interval of the plain call's bf16 value, bytes of rows that are not the call's
-    untouched, the recorded amax within 2^-8"""
+    untouched, the recorded amax within 2^-8.  Forms: the two kernels at 128-row tiles, the fused kernel's classes, and - the copy-writing
+    instantiations no other test reaches - the ring dQ kernel at both tile heights (head dim 80 has none: the knob must leave it on the
+    register-staged one)."""
+    with knobs(attn_ring=1 if form.endswith("ring") else 0):
+        _backward_e5m2_copy(form, hd, profile)
+
+
+def _backward_e5m2_copy(form, hd, profile):
     o = ops()
     D = H * hd
     qkv, dout, out, lse = _forward(hd, profile)
@@ -194,8 +205,12 @@ def test_backward_e5m2_copy(form, hd, profile):
     if form == "fused":
         calls = [(o.AttnSeqs(list(LENS), DEV, lo, hi), (seq_len > lo) & (seq_len <= hi)) for lo, hi in FUSED_CLASSES[hd] if hi <= 128]
     else:
-        calls = [(o.AttnTiles(list(LENS), DEV, tile_rows=128), torch.ones(ROWS, dtype=torch.bool))]
+        calls = [(o.AttnTiles(list(LENS), DEV, tile_rows=64 if "_64" in form else 128), torch.ones(ROWS, dtype=torch.bool))]
     for which, mine in calls:
+        if form == "fused":
+            assert attn_reached(PASS_FUSED, which, H, hd, g8=1) == [(A_FUSED, 96 if hd == 80 else hd, which.max_len // 32, 1)]
+        else:
+            assert attn_reached(PASS_BWD, which, H, hd, g8=1) == attn_meant(hd, which.tile_rows, form.endswith("ring"), g8=1)[1]
         def run(rec=None, kv_bf16=True):
             dqkv = torch.full_like(qkv, rw.SENTINEL[BF])
             d8 = torch.full(qkv.shape, rw.SENTINEL[U8], dtype=U8, device=DEV) if rec is not None else None
@@ -236,6 +251,7 @@ def test_forward_e4m3_copy(hd, tile_rows, profile):
     c = _ref(hd, profile)[0]
     qkv = _attn_buffers(c, LENS, H, hd, ROWS)[0]
     tiles = o.AttnTiles(list(LENS), DEV, tile_rows=tile_rows)
+    assert attn_reached(PASS_FWD, tiles, H, hd, g8=1) == attn_reached(PASS_FWD, tiles, H, hd) == attn_meant(hd, tile_rows)[0]      # one kernel, with and without the copy
 
     def run(rec=None):
         out, chk = rw.guarded(ROWS, D, BF, DEV)

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.test_rowwise_gpu import A_FUSED, A_FUSED224, PASS_BWD, PASS_FUSED, PASS_FWD, attn_meant, attn_reached
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -548,6 +550,7 @@ def test_attention_fwd_bwd(H, hd, lens, tile_rows):
     x[:, :D] *= o.attn_q_scale(hd)              # the kernels take q pre-multiplied by hd^-0.5 * log2(e) (qkv GEMM epilogue)
     qkv[:rows] = bf(x)
     tiles = o.AttnTiles(lens, DEV, tile_rows=tile_rows)
+    assert (attn_reached(PASS_FWD, tiles, H, hd), attn_reached(PASS_BWD, tiles, H, hd)) == attn_meant(hd, tile_rows)
     out = torch.zeros(rp, D, device=DEV, dtype=torch.bfloat16)
     lse = torch.zeros(H, rp, device=DEV)
     o.attn_fwd(qkv, tiles, H, out, lse)
@@ -599,6 +602,7 @@ def test_attention_ring_kernels_match_the_register_staged_ones(H, hd, tile_rows)
 
     def run(ring):
         _lib.tuning_set("attn_ring", ring)
+        assert (attn_reached(PASS_FWD, tiles, H, hd), attn_reached(PASS_BWD, tiles, H, hd)) == attn_meant(hd, tile_rows, ring)
         out = torch.full((rp, D), 3.0, device=DEV, dtype=torch.bfloat16)
         lse = torch.full((H, rp), 5.0, device=DEV)
         o.attn_fwd(qkv, tiles, H, out, lse)
@@ -650,6 +654,7 @@ def test_attention_bwd_fused_matches_two_kernel_form(H, hd):
             continue
         sq = o.AttnSeqs(lens, DEV, lo, hi)
         assert sq.nseq == sum(1 for L in lens if lo < L <= hi)
+        assert attn_reached(PASS_FUSED, sq, H, hd) == [(A_FUSED224 if hi == 224 else A_FUSED, 96 if hd == 80 else hd, hi // 32, 0)]
         o.attn_bwd_fused(qkv, sq, H, out, dout, lse, got)
     r0 = 0
     for L in lens:
@@ -752,6 +757,9 @@ def test_attention_bwd_writes_the_e5m2_copy_of_dqkv(H, hd):
     cut = 64 if hd == 80 else 128             # (head dim 80: the fused kernel has the 64-row form only)
     tiles = o.AttnTiles(lens, DEV, tile_rows=tr, min_len=cut)
     fused = [sq for sq in (o.AttnSeqs(lens, DEV, 0, 64), o.AttnSeqs(lens, DEV, 64, cut)) if sq.nseq]
+    # the copy-writing instantiations: dQ and dK/dV at 64-row tiles, the fused kernel at 64 (and 128) rows
+    assert tiles.ntiles and attn_reached(PASS_BWD, tiles, H, hd, g8=1) == attn_meant(hd, tr, g8=1)[1]
+    assert [attn_reached(PASS_FUSED, sq, H, hd, g8=1) for sq in fused] == [[(A_FUSED, 96 if hd == 80 else hd, r // 32, 1)] for r in ((64,) if hd == 80 else (64, 128))]
 
     def run(d8=None, rec=None, kv_bf16=True):
         dq = torch.zeros_like(qkv)
@@ -1130,6 +1138,7 @@ def test_attention_with_query_rows_limited_and_compact_output(H, hd, L, lq):
     qkv[:rows] = bf(x)
     tiles = o.AttnTiles([L] * nseq, DEV, tile_rows=128)
     assert tiles.uniform_len == L
+    assert (attn_reached(PASS_FWD, tiles, H, hd, lq=lq), attn_reached(PASS_BWD, tiles, H, hd, lq=lq)) == attn_meant(hd, 128)
     out = torch.zeros(rp, D, device=DEV, dtype=torch.bfloat16)
     lse = torch.zeros(H, rp, device=DEV)
     o.attn_fwd(qkv, tiles, H, out, lse)

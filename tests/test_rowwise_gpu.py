@@ -85,6 +85,29 @@ def tn_plan(M, N1, N2):
     return tile.value, splits.value
 
 
+A_FWD, A_FWD_RING, A_DQ, A_DQ_RING, A_DKV, A_FUSED, A_FUSED224 = range(7)      # avs_attn_launch_plan's kernel families
+PASS_FWD, PASS_BWD, PASS_FUSED = range(3)                                        # ... and passes
+
+
+def attn_reached(pas, which, H, hd, g8=0, lq=0):
+    """the kernels a call on `which` (AttnTiles; AttnSeqs for the fused pass) launches under the current knobs, per dispatch:
+    [(family, LDS image width, waves, 8-bit-copy form)] - avs_attn_launch_plan, the plan the launcher consumes (include/avsiam_hip.h)"""
+    from avsiam_amd import _lib
+    rows, items = (which.max_len, which.nseq) if pas == PASS_FUSED else (which.tile_rows, which.ntiles)
+    out = (ctypes.c_int * 15)()
+    assert _lib.load().avs_attn_launch_plan(pas, hd, rows, g8, lq, items, H, out, 15) == 0
+    d = [tuple(out[1 + 7 * i: 8 + 7 * i]) for i in range(out[0])]
+    assert all(grid == items * H and block == 64 * waves for _, _, waves, _, grid, block, _ in d)
+    return [x[:4] for x in d]
+
+
+def attn_meant(hd, rows, ring=0, g8=0):
+    """the kernels a two-kernel case is meant to reach: (forward, [dQ, dK/dV]).  Head dim 80 runs in a 96-wide LDS image and has no ring form;
+    dK/dV has none at any head dim; the forward takes its 8-bit copy at run time (no kernel of its own)"""
+    w, nw, r = 96 if hd == 80 else hd, rows // 32, bool(ring) and hd != 80
+    return [(A_FWD_RING if r else A_FWD, w, nw, 0)], [(A_DQ_RING if r else A_DQ, w, nw, g8), (A_DKV, w, nw, g8)]
+
+
 _WORST = {}
 
 
@@ -369,7 +392,7 @@ def _attn_check(chk, got, ref, tol, H, case, rows_mask=None):
 
 
 @pytest.mark.parametrize("hd,tile_rows,ring", [(32, 64, 0), (32, 128, 0), (32, 64, 1), (32, 128, 1), (64, 64, 0), (64, 128, 0), (64, 64, 1), (64, 128, 1),
-                                               (80, 128, 0)])      # (hd 80: 128-row tiles only, and no ring form - attn_fwd_impl's first branch)
+                                               (80, 128, 0), (80, 64, 0)])      # (hd 80: no ring form - attn_reached says which kernels ran)
 def test_attention_per_sequence_head_and_row(hd, tile_rows, ring):
     """One packed batch of 15 sequences of 1 ... 200 tokens (one key, a tile - 1 / tile / tile + 1 for every tile size in the kernels, a tail
     of one key): out, lse, delta, dq, dk, dv of every (sequence, head, row) against fp64, tolerances 3 x the fp32 / bf16 emulation's worst row
@@ -383,6 +406,7 @@ def test_attention_per_sequence_head_and_row(hd, tile_rows, ring):
     qkv, dout, out, lse = _attn_buffers(c, lens, H, hd, rows)
     tiles = o.AttnTiles(list(lens), DEV, tile_rows=tile_rows)
     with knobs(attn_ring=ring):
+        assert (attn_reached(PASS_FWD, tiles, H, hd), attn_reached(PASS_BWD, tiles, H, hd)) == attn_meant(hd, tile_rows, ring)
         o.attn_fwd(qkv, tiles, H, out, lse)
         dqkv = torch.full_like(qkv, rw.SENTINEL[BF])
         delta = torch.full_like(lse, rw.SENTINEL[F32])
@@ -411,6 +435,7 @@ def test_attention_fused_backward_length_classes(hd):
     for lo, hi in {32: ((0, 64), (64, 128)), 64: ((0, 64), (64, 128), (128, 224)), 80: ((0, 64),)}[hd]:
         sq = o.AttnSeqs(list(lens), DEV, lo, hi)
         assert sq.nseq == sum(1 for L in lens if lo < L <= hi) > 0
+        assert attn_reached(PASS_FUSED, sq, H, hd) == [(A_FUSED224 if hi == 224 else A_FUSED, 96 if hd == 80 else hd, hi // 32, 0)]
         dqkv = torch.full_like(qkv, rw.SENTINEL[BF])
         o.attn_bwd_fused(qkv, sq, H, out, dout, lse, dqkv)
         mine = (seq_len > lo) & (seq_len <= hi)
@@ -434,6 +459,9 @@ def test_attention_compact_queries(hd, lq):
     chk = Chk("attention_cq.hd%d" % hd)
     qkv, dout, out, lse = _attn_buffers(c, lens, H, hd, nq)
     tiles = o.AttnTiles(list(lens), DEV, tile_rows=128)
+    with knobs(attn_ring=1):                       # (the compact form has no ring kernels: the knob changes nothing)
+        assert (attn_reached(PASS_FWD, tiles, H, hd, lq=lq), attn_reached(PASS_BWD, tiles, H, hd, lq=lq)) == attn_meant(hd, 128)
+    assert (attn_reached(PASS_FWD, tiles, H, hd, lq=lq), attn_reached(PASS_BWD, tiles, H, hd, lq=lq)) == attn_meant(hd, 128)
     o.attn_fwd(qkv, tiles, H, out, lse, lq=lq)
     dqkv = torch.full_like(qkv, rw.SENTINEL[BF])
     delta = torch.full_like(lse, rw.SENTINEL[F32])

@@ -7,6 +7,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from avsiam_amd import ops  # noqa: E402
+from avsiam_amd.engine import attention_plan  # noqa: E402
 
 
 def timeit(fn, iters=5):
@@ -61,49 +62,30 @@ def run_case(name, H, hd, lens, dev, tile_rows=(128, 64)):
             tb8 = timeit(lambda: ops.attn_bwd(qkv, tiles, H, out, dout, lse, delta, dqkv, dqkv8=d8, q8=rec.rec(1)), 10)
             tb8l = timeit(lambda: ops.attn_bwd(qkv, tiles, H, out, dout, lse, delta, dqkv, dqkv8=d8, q8=rec.rec(1), kv_bf16=False), 10)
             msg += f"  [+8-bit copies] fwd {tf8*1e6:7.1f} us  bwd {tb8*1e6:7.1f} us  bwd without bf16 dK/dV {tb8l*1e6:7.1f} us"
-    if hd == 80 and min(lens) <= 64:
-        # head dim 80: the fused kernel exists for 64-row workgroups only
-        f = [ops.AttnSeqs(lens, dev, 0, 64)]
-        for tr in tile_rows:
-            tl = ops.AttnTiles(lens, dev, tile_rows=tr, min_len=64)
-
-            def mixed80():
-                if tl.ntiles:
-                    ops.attn_bwd(qkv, tl, H, out, dout, lse, delta, dqkv)
-                ops.attn_bwd_fused(qkv, f[0], H, out, dout, lse, dqkv)
-            msg += f"  [fused<=64 + tile {tr}] bwd {timeit(mixed80, 10)*1e6:7.1f} us"
-            if "--g8" in sys.argv:
-                def mixed80l():
-                    if tl.ntiles:
-                        ops.attn_bwd(qkv, tl, H, out, dout, lse, delta, dqkv, dqkv8=d8, q8=rec.rec(1), kv_bf16=False)
-                    ops.attn_bwd_fused(qkv, f[0], H, out, dout, lse, dqkv, dqkv8=d8, q8=rec.rec(1), kv_bf16=False)
-                msg += f" (lean e5m2 {timeit(mixed80l, 10)*1e6:7.1f} us)"
-    if hd in (32, 64) and min(lens) <= 128:
-        # the backward as the engine runs it: sequences of at most 128 tokens through the fused kernel, the rest through the two kernels
-        f = [sq for sq in (ops.AttnSeqs(lens, dev, 0, 64), ops.AttnSeqs(lens, dev, 64, 128)) if sq.nseq]
-        long_lens = [L for L in lens if L > 128]
-        tl = ops.AttnTiles(lens, dev, tile_rows=64 if sum(long_lens) / max(1, len(long_lens)) < 256 else 128, min_len=128)
+    # the backward as the engine runs it (engine.attention_plan: the fused classes, the cut and the tile rows of the two-kernel rest)
+    def mixed_bwd(label, lean=False, **kw):
+        p = attention_plan(lens, hd, attn_fused=True, inference=False, **kw)
+        f = [ops.AttnSeqs(lens, dev, lo, hi) for lo, hi in p.fused]
+        tl = ops.AttnTiles(lens, dev, tile_rows=p.bwd_rows, min_len=p.cut)
+        g8 = dict(dqkv8=d8, q8=rec.rec(1), kv_bf16=False) if lean else {}
 
         def mixed():
             if tl.ntiles:
-                ops.attn_bwd(qkv, tl, H, out, dout, lse, delta, dqkv)
+                ops.attn_bwd(qkv, tl, H, out, dout, lse, delta, dqkv, **g8)
             for sq in f:
-                ops.attn_bwd_fused(qkv, sq, H, out, dout, lse, dqkv)
-        tm = timeit(mixed, 10)
-        msg += f"  [fused<=128] bwd {tm*1e6:7.1f} us"
+                ops.attn_bwd_fused(qkv, sq, H, out, dout, lse, dqkv, **g8)
+        return label % dict(cut=p.cut, rows=p.bwd_rows, us=timeit(mixed, 10) * 1e6)
+    if hd == 80 and min(lens) <= 64:
+        # head dim 80: the fused kernel exists for 64-row workgroups only
+        for tr in tile_rows:
+            msg += mixed_bwd("  [fused<=%(cut)d + tile %(rows)d] bwd %(us)7.1f us", attn_tile=tr, fused224=False)
+            if "--g8" in sys.argv:
+                msg += mixed_bwd(" (lean e5m2 %(us)7.1f us)", lean=True, attn_tile=tr, fused224=False)
+    if hd in (32, 64) and min(lens) <= 128:
+        msg += mixed_bwd("  [fused<=%(cut)d] bwd %(us)7.1f us", attn_tile=0, fused224=False)
         if hd == 64 and any(128 < L <= 224 for L in lens):
-            # round 6: sequences of 129 .. 224 tokens through the 7-wave fused kernel as well (what the engine runs now)
-            f2 = f + [ops.AttnSeqs(lens, dev, 128, 224)]
-            ll = [L for L in lens if L > 224]
-            tl2 = ops.AttnTiles(lens, dev, tile_rows=64 if sum(ll) / max(1, len(ll)) < 256 else 128, min_len=224)
-
-            def mixed2():
-                if tl2.ntiles:
-                    ops.attn_bwd(qkv, tl2, H, out, dout, lse, delta, dqkv)
-                for sq in f2:
-                    ops.attn_bwd_fused(qkv, sq, H, out, dout, lse, dqkv)
-            tm2 = timeit(mixed2, 10)
-            msg += f"  [fused<=224] bwd {tm2*1e6:7.1f} us"
+            # round 6: sequences of 129 .. 224 tokens through the 7-wave fused kernel as well
+            msg += mixed_bwd("  [fused<=%(cut)d] bwd %(us)7.1f us", attn_tile=0, fused224=True)
     print(msg, flush=True)
 
 
